@@ -16,6 +16,12 @@ per-worker shard is 256 = its 1024 global batch over 4 workers, `settings_dist.p
 
 Rank 0 prints ONE JSON line; ``value`` is whole-job images/sec computed from the
 MAX over ranks of the timed wall time.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line.  ``--full``
+adds the communication diagnostics after the timed region (``comm`` then carries the
+per-bucket allreduce times and the overlapped / serial / compute-only step A/B; a plain
+run reports only the bucket plan there).  ``--dump-outputs DIR`` writes what the last
+timed step computed as ``DIR/<name>.npy`` (``dump_outputs`` below).
 """
 
 import argparse
@@ -62,8 +68,14 @@ def parse():
                    help="1: create the process group and issue the bucket collectives even at one rank "
                         "(exercises the RCCL path on a 1-GPU box; the timed step then includes them)")
     p.add_argument("--comm_diag", type=int, default=1,
-                   help="N > 1: after the timed steps, measure per-bucket allreduce time and the exposed "
-                        "communication (A/B against compute-only and non-overlapped steps)")
+                   help="with --full at N > 1: after the timed steps, measure per-bucket allreduce time and the "
+                        "exposed communication (A/B against compute-only and non-overlapped steps)")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the communication diagnostics "
+                        "(--comm_diag), which take extra collectives and extra steps after the timed region")
+    p.add_argument("--dump-outputs", dest="dump_outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed (loss sums, head "
+                        "predictions, gradients, updated parameters) as DIR/<name>.npy (float32)")
     return p.parse_args()
 
 
@@ -87,7 +99,7 @@ def comm_diagnostics(a, ctx, flat, bounds, sync_overlap, step_fn, dev):
     from unet_distributed_amd.parallel.grad_sync import GradSync
     out = {"backend": ctx.backend or "none", "world_size": ctx.world_size,
            "buckets_mb": [round(4.0 * (b - (bounds[i - 1] if i else 0)) / 2 ** 20, 3) for i, b in enumerate(bounds)]}
-    if (ctx.world_size == 1 and not a.dist_force) or not ctx.initialized or not a.comm_diag:
+    if not a.full or (ctx.world_size == 1 and not a.dist_force) or not ctx.initialized or not a.comm_diag:
         return out
     per = []
     for i in range(len(bounds)):
@@ -136,6 +148,32 @@ def comm_diagnostics(a, ctx, flat, bounds, sync_overlap, step_fn, dev):
                step_ms_serial_comm=round(t_ser, 3), exposed_comm_ms=round(t_ovl - t_none, 3),
                serial_comm_ms=round(t_ser - t_none, 3))
     return out
+
+
+DUMP_MAX_ELEMS = 4 * 2 ** 20       # per array: 16 MiB of float32, four arrays stay well under 64 MB
+
+
+def dump_outputs(path, backend, flat):
+    """What a caller of the timed step holds after its last step, as ``path/<name>.npy``
+    (float32): the loss sums {I, St, Sp, BCE_sum}, the head's predictions for the batch,
+    the flat gradient and the updated flat parameters.  An array above DUMP_MAX_ELEMS
+    elements is written as a fixed sample of that many (sorted indices drawn without
+    replacement from a generator seeded with the array's length), so two builds given the
+    same arguments write the same elements."""
+    import numpy as np
+    if hasattr(backend, "engine"):
+        pred = backend.engine.probs()
+    else:
+        pred = backend._last[2]
+    arrays = {"loss_sums": backend.sums(), "predictions": pred, "grad": flat.grad, "params": flat.master}
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(n).choice(n, DUMP_MAX_ELEMS, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def main():
@@ -219,6 +257,8 @@ def main():
         os.makedirs(a.profile_dir, exist_ok=True)
         prof.export_chrome_trace(os.path.join(a.profile_dir, "trace.json"))
     dt = D.allreduce_max_scalar(dt, dev)
+    if a.dump_outputs and ctx.rank == 0:
+        dump_outputs(a.dump_outputs, backend, flat)
     imgs = a.steps * B * N
     s = backend.sums()
     i_, st, sp = [float(v) for v in s[:3].tolist()]

@@ -15,7 +15,7 @@ for ch in default 8 16; do
     env_ch=""
     [ "$ch" != default ] && env_ch="NCCL_MIN_NCHANNELS=$ch"
     env $env_ch timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-      --master-addr 127.0.0.1 --master-port $port bench.py --gpus $N --steps 20 --warmup 5 --bucket_mb $mb \
+      --master-addr 127.0.0.1 --master-port $port bench.py --gpus $N --steps 20 --warmup 5 --bucket_mb $mb --full \
       > gpurun_out/sweep/${mb}_${ch}.log 2>&1 || { echo "bucket $mb ch $ch failed"; tail -5 gpurun_out/sweep/${mb}_${ch}.log; exit 1; }
     grep '^{' gpurun_out/sweep/${mb}_${ch}.log > gpurun_out/sweep/${mb}_${ch}.json
   done

@@ -41,7 +41,7 @@ for n in 1 2 4 8; do
     row 1 - - $log
     log=gpurun_out/scale/n1_force.log
     MASTER_ADDR=127.0.0.1 MASTER_PORT=$port RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 \
-      timeout -k 10 300 python bench.py --gpus 1 --dist_force 1 "$@" > $log 2>&1 || exit $?
+      timeout -k 10 300 python bench.py --gpus 1 --dist_force 1 --full "$@" > $log 2>&1 || exit $?
     row "1 (RCCL one-rank)" 8 - $log
     continue
   fi
@@ -51,7 +51,7 @@ for n in 1 2 4 8; do
       log=gpurun_out/scale/n${n}_b${b}_c${ch}.log
       if [ $ch = unset ]; then envc=""; else envc="NCCL_MIN_NCHANNELS=$ch"; fi
       env $envc timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-        --master-addr 127.0.0.1 --master-port $port bench.py --gpus $n --bucket_mb $b "$@" > $log 2>&1 || exit $?
+        --master-addr 127.0.0.1 --master-port $port bench.py --gpus $n --bucket_mb $b --full "$@" > $log 2>&1 || exit $?
       row $n $b $ch $log
     done
   done

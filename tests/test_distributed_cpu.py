@@ -263,11 +263,61 @@ def test_bench_py_two_ranks_gloo_cpu():
     compute-only A/B) on two CPU ranks over gloo with the ATen backend -- the same command
     shape the driver's 8-GPU lease runs (`test_dist.py:385-398`: every worker's sharded step)."""
     r = _run_bench(["--backend", "torch", "--dtype", "fp32", "--per_gpu_batch", "2", "--img_size", "64",
-                    "--steps", "2", "--warmup", "1"])
+                    "--steps", "2", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stdout[-3000:]
     rec = bench_record(r.stdout)
     check_multirank_bench(rec, 2)
     assert rec["comm"]["backend"] == "gloo" and rec["config"]["backend"] == "torch"
+
+
+def test_bench_py_plain_run_skips_comm_diagnostics():
+    """Without --full the communication diagnostics return the bucket plan alone, before
+    any collective or extra step (the stand-in arguments would fail on first use)."""
+    import argparse
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    ctx = types.SimpleNamespace(backend="gloo", world_size=2, initialized=True, rank=0)
+    bounds = [1 << 20, 3 << 20]
+    for full in (False, True):
+        a = argparse.Namespace(full=full, dist_force=0, comm_diag=1)
+        if full:
+            with pytest.raises(AttributeError):     # goes on to time the buckets: sync_overlap is needed
+                bench.comm_diagnostics(a, ctx, None, bounds, None, None, torch.device("cpu"))
+        else:
+            out = bench.comm_diagnostics(a, ctx, None, bounds, None, None, torch.device("cpu"))
+            assert out == {"backend": "gloo", "world_size": 2, "buckets_mb": [4.0, 8.0]}
+
+
+def test_bench_py_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's loss sums, predictions, gradient and
+    updated parameters as float32 .npy files (at most 64 MB in all, large arrays as a fixed
+    sample), identical from run to run with the same arguments; --steps sets the number of
+    timed steps and the line carries ms_per_step."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / ("dump%d" % k))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "torch",
+                            "--dtype", "fp32", "--per_gpu_batch", "2", "--img_size", "32", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", d], env=env, stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-3000:]
+        rec = bench_record(r.stdout)
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and "allreduce_ms_per_bucket" not in rec["comm"]
+        assert abs(rec["value"] - 2 * 1000.0 / rec["ms_per_step"]) <= 0.01 * rec["value"]
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64e6
+    assert sorted(dumps[0]) == ["grad", "loss_sums", "params", "predictions"]
+    n_params = 7760385
+    for name, n in (("loss_sums", 4), ("predictions", 2 * 32 * 32), ("grad", min(n_params, bench.DUMP_MAX_ELEMS)),
+                    ("params", min(n_params, bench.DUMP_MAX_ELEMS))):
+        x = dumps[0][name]
+        assert x.dtype == np.float32 and x.shape == (n,) and np.isfinite(x).all() and np.abs(x).max() > 0, name
+        assert np.array_equal(x, dumps[1][name]), name
 
 
 @pytest.mark.slow
@@ -277,7 +327,7 @@ def test_bench_py_eight_ranks_gloo_cpu():
     line with n_gpus / global_batch / parallelism of the 8-rank job, every bucket gets an
     allreduce time and the exposed-communication A/B is reported (`test_dist.py:385-398`)."""
     r = _run_bench(["--backend", "torch", "--dtype", "fp32", "--per_gpu_batch", "1", "--img_size", "32",
-                    "--steps", "2", "--warmup", "1", "--bucket_mb", "4"], nproc=8,
+                    "--steps", "2", "--warmup", "1", "--bucket_mb", "4", "--full"], nproc=8,
                    env_extra={"OMP_NUM_THREADS": "1"})
     assert r.returncode == 0, r.stdout[-3000:]
     rec = bench_record(r.stdout)

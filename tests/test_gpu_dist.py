@@ -165,7 +165,7 @@ def test_bench_py_two_ranks_one_card_native():
     run does."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_distributed_cpu import _run_bench, bench_record, check_multirank_bench
-    r = _run_bench(["--per_gpu_batch", "64", "--steps", "3", "--warmup", "2"], timeout=300,
+    r = _run_bench(["--per_gpu_batch", "64", "--steps", "3", "--warmup", "2", "--full"], timeout=300,
                    env_extra=dict(UNET_DIST_BACKEND="gloo"))
     assert r.returncode == 0, r.stdout[-3000:]
     rec = bench_record(r.stdout)

@@ -119,13 +119,14 @@ def test_rccl_one_rank_bucket_path_orders_streams(tmp_path):
 
 
 def test_bench_dist_force_one_rank_reports_rccl_buckets():
-    """bench.py --dist_force 1 at one rank: the timed step includes the RCCL bucket
+    """bench.py --dist_force 1 --full at one rank: the timed step includes the RCCL bucket
     allreduces and the JSON carries the comm diagnostics (per-bucket RCCL time)."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0")
     env.pop("UNET_DIST_BACKEND", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dist_force", "1", "--per_gpu_batch", "64",
-                        "--steps", "3", "--warmup", "2"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                        "--steps", "3", "--warmup", "2", "--full"], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT,
                        text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
