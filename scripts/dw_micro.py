@@ -1,7 +1,8 @@
 """Isolated timings of the fused data + weight gradient (conv_dw.hip) at the benched
 level-1 shape (2D, 128 wide, 32 -> 32 channels, per-GPU batch 1024) for each operand
 source: plain dY (XF 0), norm backward on load (XF 2), the normalised head (XF 3) and
-the norm-free head (XF 4).  Usage on the GPU box: python scripts/dw_micro.py [N] [reps]"""
+the norm-free head (XF 4), each with the serial and the pipelined window loop (fw_pipe 0 / 1)
+in alternating rounds.  Usage on the GPU box: python scripts/dw_micro.py [N] [reps] [rounds]"""
 import os
 import sys
 
@@ -18,6 +19,7 @@ def ptr(t):
 def main():
     N = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+    rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 3
     H = W = 128
     P = N * H * W
     C = native.require()
@@ -50,7 +52,7 @@ def main():
         "XF3 dgrad-norm": dict(base, **norm, **xf2, **hg, src1=ptr(z), hg_fa=ptr(co[5]), hg_fc=ptr(co[6])),
         "XF4 dgrad bits": dict(base, mask1=ptr(bits), mask_bits=1, **hg, hg_bits=ptr(bits)),
     }
-    for name, d in variants.items():
+    def timed(d):
         for _ in range(3):
             C.conv_fwd(d, s)
         torch.cuda.synchronize()
@@ -60,7 +62,17 @@ def main():
             C.conv_fwd(d, s)
         e1.record()
         torch.cuda.synchronize()
-        print("| %s | %.4f |" % (name, e0.elapsed_time(e1) / reps))
+        return e0.elapsed_time(e1) / reps
+
+    # each operand source with the serial (fw_pipe=0) and the pipelined window loop
+    # (fw_pipe=1; variants without one run the serial loop either way), alternating
+    print("| variant | fw_pipe=0 ms (rounds) | fw_pipe=1 ms (rounds) |")
+    for name, d in variants.items():
+        ms = {0: [], 1: []}
+        for _ in range(rounds):
+            for pipe in (0, 1):
+                ms[pipe].append(timed(dict(d, fw_pipe=pipe)))
+        print("| %s | %s | %s |" % (name, " ".join("%.4f" % v for v in ms[0]), " ".join("%.4f" % v for v in ms[1])))
 
 
 if __name__ == "__main__":

@@ -96,10 +96,23 @@ __device__ __forceinline__ void dw_dlogit(const ConvFwdParams& p, const float (&
 // walked segment-major (segment s = window / (rows / R)), so consecutive windows of a
 // workgroup are consecutive row pairs of one segment and the halo-row carry still holds;
 // the halo columns -1 / 128 are the neighbouring segments' pixels (zeros at the row ends).
-template <int EPI, int XF, bool SEG = false>
+//
+// PIPE: the pipelined window loop (below, after the serial one).  The serial loop runs each
+// window as a chain of exposed waits: barrier, halo + x image DMA, wait, MFMAs, staging,
+// ReLU-mask loads, wait, stores.  The pipelined loop issues the NEXT window's loads under
+// the current window's data-gradient MFMAs and epilogue -- the x image by LDS-DMA into As
+// (free once the weight-gradient MFMAs are done), the two new dY halo rows of a carried
+// window (XF 4: their probability / target / ReLU bits) into registers, since their LDS
+// rows hold the epilogue's staging tile until the window ends -- and the ReLU-mask bytes of
+// the epilogue at the window top.  Between the prefetch and the next window top every
+// barrier is an lds_barrier() (conv_epilogue.h) and no ordinary load is used, so nothing
+// drains the prefetch early.  Same LDS image, same MFMA operands and order: bit-identical
+// results.  Plain EPI_DGRAD of whole 128-wide rows with a 1-bit (or no) ReLU mask only.
+template <int EPI, int XF, bool SEG = false, bool PIPE = false>
 __global__ void __launch_bounds__(DW_NTHR, 2) conv_dw_kernel(const ConvFwdParams p) {
   static_assert(XF == 0 || XF == 2 || XF == 3 || XF == 4,
                 "plain dY, norm backward on load (of the normalised head), head gradient on load");
+  static_assert(!PIPE || (EPI == EPI_DGRAD && (XF == 0 || XF == 4) && !SEG), "variants with a pipelined loop");
   constexpr int W = DW_W, R = DW_R, HR = DW_HR, ROWB = DW_ROWB, BN = DW_BN;
   constexpr int TM = 4, TN = 2, TC = 2, RW = 2, NCS = 4;   // data-gradient strip: 2 rows x 32 columns per wave
   __shared__ __attribute__((aligned(1024))) char smem[DW_LDS];
@@ -208,6 +221,93 @@ __global__ void __launch_bounds__(DW_NTHR, 2) conv_dw_kernel(const ConvFwdParams
   // hr ROWB +- 2 fl ROWB.
   int fl = 0;
 
+  // The MFMA phases of a window (fo: physical offset of logical halo rows 0, 1), shared by
+  // the serial and the pipelined loop.
+  // ---- weight gradient: halo row hr at shift dw feeds x rows y = hr - 2 + dh
+  auto wgrad_mfmas = [&](const int fo) {
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+      const int so = (sw0 + st) * 32 * 64;
+      h16x8 xa[R][2];
+#pragma unroll
+      for (int y = 0; y < R; ++y)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int a = (abase ^ (32 * i)) + y * W * 64 + so;
+          xa[y][i] = tr8(As + a, As + a + 512);
+        }
+#pragma unroll
+      for (int hr = 0; hr < HR; ++hr) {
+#pragma unroll
+        for (int dw = 0; dw < 3; ++dw) {
+          const int a = dbase[dw] + hr * ROWB + so + (hr < 2 ? fo : -fo);
+          const h16x8 yb = tr8(Xs + a, Xs + a + 512);
+          if (dw == 1 && hr >= 1 && hr <= R) bacc = mfma16(ones, yb, bacc);   // the window's own dY: bias sums
+#pragma unroll
+          for (int dh = 0; dh < 3; ++dh) {
+            const int y = hr - 2 + dh;
+            if (y < 0 || y >= R) continue;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) wacc[3 * dh + dw][i] = mfma16(xa[y][i], yb, wacc[3 * dh + dw][i]);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  };
+  // ---- data gradient (conv_win.h chunk_mfmas, one 32-channel chunk)
+  auto dgrad_mfmas = [&](f32x4 (&acc)[TM][TN], const int fo) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dw = 0; dw < 3; ++dw) {
+      h16x8 wf[3][TN];
+#pragma unroll
+      for (int dh = 0; dh < 3; ++dh)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) wf[dh][j] = *(const h16x8*)(Ws + ((3 * dh + dw) * BN + 16 * j) * 64 + wbase);
+#pragma unroll
+      for (int hr = 0; hr < RW + 2; ++hr) {
+#pragma unroll
+        for (int ci = 0; ci < TC; ++ci) {
+          const h16x8 xf = *(const h16x8*)(Xs + xbase[dw] + hr * ROWB + ci * 16 * 64 + (hr < 2 ? fo : -fo));
+#pragma unroll
+          for (int dh = 0; dh < 3; ++dh) {
+            const int ri = hr - dh;
+            if (ri < 0 || ri >= RW) continue;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[ri * TC + ci][j] = mfma16(wf[dh][j], xf, acc[ri * TC + ci][j]);
+          }
+        }
+      }
+    }
+  };
+  // XF 4: dY = dlogit w (x > 0) per slot (head_grad.h head_grad_pixel) of halo granules
+  // k0 + tid + 256 j, zeros outside the image (hbits 0 there)
+  auto form_head_dy = [&](const int k0, const int fl, const auto& dl, const auto& hbits) {
+    if constexpr (XF == 4) {
+      float hw[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) hw[e] = Ks[kch + e];
+#pragma unroll
+      for (int j = 0; j < DW_HJ; ++j) {
+        const int k = k0 + tid + DW_NTHR * j;
+        if (k >= DW_HG) continue;
+        const int hr = k / (DW_HWP * 4), s = (k >> 2) - hr * DW_HWP;
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float v = dl[j] * hw[e];
+          o[e] = ((hbits[j] >> e) & 1u) ? v : 0.f;
+        }
+        *(u32x4*)(Xs + ((hr ^ (2 * fl)) * DW_HWP + s) * 64 + 16 * ((tid & 3) ^ ((s >> 1) & 3))) = pack8(o);
+      }
+    }
+  };
+
+  if constexpr (!PIPE)
   for (int win = w_begin; win < w_end; ++win) {
     const int seg = SEG ? win / nrp : 0;
     const int col0 = seg * W;                          // the window's first column
@@ -311,23 +411,7 @@ __global__ void __launch_bounds__(DW_NTHR, 2) conv_dw_kernel(const ConvFwdParams
     // target loads overlap the x image DMA instead of being waited on before it)
     if constexpr (XF >= 3) dw_dlogit<XF>(p, pr, tv, dl);
     if constexpr (XF == 4) {
-      // dY = dlogit w (x > 0) per slot (head_grad.h head_grad_pixel), zeros outside the image
-      float hw[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) hw[e] = Ks[kch + e];
-#pragma unroll
-      for (int j = 0; j < DW_HJ; ++j) {
-        const int k = k0 + tid + DW_NTHR * j;
-        if (k >= DW_HG) continue;
-        const int hr = k / (DW_HWP * 4), s = (k >> 2) - hr * DW_HWP;
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float v = dl[j] * hw[e];
-          o[e] = ((hbits[j] >> e) & 1u) ? v : 0.f;
-        }
-        *(u32x4*)(Xs + ((hr ^ (2 * fl)) * DW_HWP + s) * 64 + 16 * ((tid & 3) ^ ((s >> 1) & 3))) = pack8(o);
-      }
+      form_head_dy(k0, fl, dl, hbits);
       __syncthreads();
     } else if constexpr (XF >= 2) {
       // dz = fmaf(ca, g, fmaf(cb, z, cc)) in place (16-byte granule k of the halo: LDS
@@ -373,65 +457,9 @@ __global__ void __launch_bounds__(DW_NTHR, 2) conv_dw_kernel(const ConvFwdParams
       __syncthreads();
     }
 
-    // ---- weight gradient: halo row hr at shift dw feeds x rows y = hr - 2 + dh
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-      const int so = (sw0 + st) * 32 * 64;
-      h16x8 xa[R][2];
-#pragma unroll
-      for (int y = 0; y < R; ++y)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int a = (abase ^ (32 * i)) + y * W * 64 + so;
-          xa[y][i] = tr8(As + a, As + a + 512);
-        }
-#pragma unroll
-      for (int hr = 0; hr < HR; ++hr) {
-#pragma unroll
-        for (int dw = 0; dw < 3; ++dw) {
-          const int a = dbase[dw] + hr * ROWB + so + (hr < 2 ? fo : -fo);
-          const h16x8 yb = tr8(Xs + a, Xs + a + 512);
-          if (dw == 1 && hr >= 1 && hr <= R) bacc = mfma16(ones, yb, bacc);   // the window's own dY: bias sums
-#pragma unroll
-          for (int dh = 0; dh < 3; ++dh) {
-            const int y = hr - 2 + dh;
-            if (y < 0 || y >= R) continue;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) wacc[3 * dh + dw][i] = mfma16(xa[y][i], yb, wacc[3 * dh + dw][i]);
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-
-    // ---- data gradient (conv_win.h chunk_mfmas, one 32-channel chunk)
+    wgrad_mfmas(fo);
     f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dw = 0; dw < 3; ++dw) {
-      h16x8 wf[3][TN];
-#pragma unroll
-      for (int dh = 0; dh < 3; ++dh)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) wf[dh][j] = *(const h16x8*)(Ws + ((3 * dh + dw) * BN + 16 * j) * 64 + wbase);
-#pragma unroll
-      for (int hr = 0; hr < RW + 2; ++hr) {
-#pragma unroll
-        for (int ci = 0; ci < TC; ++ci) {
-          const h16x8 xf = *(const h16x8*)(Xs + xbase[dw] + hr * ROWB + ci * 16 * 64 + (hr < 2 ? fo : -fo));
-#pragma unroll
-          for (int dh = 0; dh < 3; ++dh) {
-            const int ri = hr - dh;
-            if (ri < 0 || ri >= RW) continue;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[ri * TC + ci][j] = mfma16(wf[dh][j], xf, acc[ri * TC + ci][j]);
-          }
-        }
-      }
-    }
+    dgrad_mfmas(acc, fo);
     __syncthreads();      // every wave is done reading the halo image (the staging tile aliases rows 0, 1)
     using Map = StripTiles<W, RW, TC, NCS>;
     if constexpr (SEG)
@@ -440,6 +468,173 @@ __global__ void __launch_bounds__(DW_NTHR, 2) conv_dw_kernel(const ConvFwdParams
     else
       conv_epilogue<DW_BM, BN, DW_BM / 4, BN, TM, TN, DW_NTHR, EPI, Map, 0, W>(p, acc, Xs + fo, g0 * W, 0, M, wave, 0,
                                                                               lane, tid, 0, 0, win);
+  }
+
+  // ---- the pipelined loop (PIPE, see the head comment)
+  if constexpr (PIPE) {
+    constexpr int NPF = 5;                             // prefetched pieces (XF 4: granules) per thread
+    static_assert(2 * NPF >= DW_PPR && NPF * DW_NTHR >= DW_HG / 2, "two halo rows in NPF passes");
+    // x image of window w into As (the serial loop's DMA)
+    auto x_dma = [&](const int w) {
+      const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(
+          (void*)((const char*)p.fw.x + (size_t)w * R * W * Cx * 2), (short)0, OOB, 0x00020000);
+#pragma unroll
+      for (int i = 0; i < DW_AI / 4; ++i) {
+        const int k = 4 * wave + i;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsx, (__attribute__((address_space(3))) void*)(As + k * 1024), 16,
+                                                 xdma_lane + k * 1024, 0, 0, 0);
+      }
+    };
+    // XF 4: probability / target / ReLU-bit byte of halo granules k0 + tid + 256 j of the
+    // window at row g0, as whole dwords: the pixel pair's targets and the pixel's four bit
+    // bytes (launch_conv_dw checks the alignment).  The thread's half / byte is picked, and
+    // masked by okm, where the values are used: a narrow load's widening or a select here
+    // would be a use, which waits for the load.
+    auto head_loads = [&](const int g0, const bool top_in, const bool bot_in, const int k0, auto& pr, auto& tv,
+                          auto& hb, uint32_t& okm) {
+      constexpr int NJ = sizeof(pr) / sizeof(pr[0]);
+      okm = 0;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int k = k0 + tid + DW_NTHR * j;
+        const int hr = k / (DW_HWP * 4), s = (k >> 2) - hr * DW_HWP;
+        const int gr = g0 - 1 + hr, col = s - 1;
+        const bool ok = k < DW_HG && (hr > 0 || top_in) && (hr < R + 1 || bot_in) &&
+                        (unsigned)gr < (unsigned)rows_total && (unsigned)col < (unsigned)W && s <= W + 1;
+        okm |= (ok ? 1u : 0u) << j;
+        const int pix = ok ? gr * W + col : 0;
+        pr[j] = p.hg.prob[pix];
+        tv[j] = ((const uint32_t*)p.hg.t)[pix >> 1];
+        hb[j] = ((const uint32_t*)p.hg.bits)[pix];
+      }
+    };
+    u32x4 nhv[XF == 0 ? NPF : 1];                      // the next carried window's two dY rows (XF 0) ...
+    float npr[XF == 4 ? NPF : 1];                      // ... or their granules' probability / target / bits
+    uint32_t ntv[XF == 4 ? NPF : 1], nhb[XF == 4 ? NPF : 1], nokm = 0;
+#pragma unroll
+    for (int i = 0; i < (XF == 0 ? NPF : 1); ++i) nhv[i] = (u32x4){0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < (XF == 4 ? NPF : 1); ++i) {
+      npr[i] = 0.f;
+      ntv[i] = nhb[i] = 0u;
+    }
+    // XF 4: the scalars of dw_dlogit, the same for every window
+    float hd_a = 0.f, hd_b = 0.f, hd_gs = 1.f;
+    if constexpr (XF == 4) {
+      const float I = p.hg.sums[0], St = p.hg.sums[1], Sp = p.hg.sums[2];
+      hd_a = -2.f / (2.f * I + 1.f);
+      hd_b = 1.f / (St + Sp + 1.f);
+      hd_gs = p.hg.gscale ? *p.hg.gscale : 1.f;
+    }
+    if constexpr (XF == 4) {
+      if (tid < 32) Ks[tid] = p.hg.w[tid];            // the head weights: once (read after the first barrier)
+    }
+    if (w_begin < w_end) x_dma(w_begin);
+    // a carried window's pieces of halo row 2 + (wave >> 1): waves 2 i, 2 i + 1 its two halves
+    const int pj0 = NPF * (wave & 1);
+
+    for (int win = w_begin; win < w_end; ++win) {
+      const int g0 = win * R;
+      const int grow0 = (g0 / H) * H;
+      const bool top_in = (g0 % H) != 0, bot_in = ((g0 + R) % H) != 0;
+      const bool carry = win > w_begin && top_in;     // (wave-uniform)
+      if (carry) fl ^= 1;
+      const int fo = fl * 2 * ROWB;
+      const int k0 = carry ? 2 * DW_HWP * 4 : 0;
+      const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
+          (void*)((const char*)p.src1 + (size_t)grow0 * W * C * 2), (short)0, OOB, 0x00020000);
+      // ---- window top.  In flight: this window's x image DMA and register prefetch, the
+      // previous window's stores.  (The wait stands in straight-line code behind the barrier:
+      // inside the two arms below the compiler could not tell that every path has it, and
+      // would wait for the mask loads before the first read of As.)
+      lds_barrier();        // the previous window's epilogue is done with the staging tile
+      __builtin_amdgcn_s_waitcnt(kWaitVm0);
+      float pr[XF == 4 ? DW_HJ : 1];
+      uint32_t tv[XF == 4 ? DW_HJ : 1], hb[XF == 4 ? DW_HJ : 1], okm = nokm;
+      if constexpr (XF == 0) {
+        if (!carry) {       // whole halo, waited for here: wave w fills row w (the serial loop's DMA)
+          const int gr = g0 - 1 + wave;
+          const bool row_ok = (wave > 0 || top_in) && (wave < R + 1 || bot_in) && (unsigned)gr < (unsigned)rows_total;
+          const int rowoff = (gr - grow0) * W * C * 2;
+          char* hdst = Xs + (wave ^ (2 * fl)) * ROWB;
+#pragma unroll
+          for (int j = 0; j < DW_PPR; ++j) {
+            const bool ok = row_ok && (unsigned)(16 * j + lslot - 1) < (unsigned)W;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (__attribute__((address_space(3))) void*)(hdst + j * 1024),
+                                                     16, ok ? rowoff + dma_lane + j * 1024 : OOB, 0, 0, 0);
+          }
+          __builtin_amdgcn_s_waitcnt(kWaitVm0);
+        } else {            // the prefetched rows 2, 3, where the DMA would have put them
+          char* hdst = Xs + ((2 + (wave >> 1)) ^ (2 * fl)) * ROWB;
+#pragma unroll
+          for (int i = 0; i < NPF; ++i)
+            if (pj0 + i < DW_PPR) *(u32x4*)(hdst + (pj0 + i) * 1024 + lane * 16) = nhv[i];
+        }
+      } else {
+        if (!carry) {
+          head_loads(g0, top_in, bot_in, 0, pr, tv, hb, okm);
+        } else {
+#pragma unroll
+          for (int j = 0; j < DW_HJ; ++j) {
+            pr[j] = j < NPF ? npr[j < NPF ? j : 0] : 0.f;
+            tv[j] = j < NPF ? ntv[j < NPF ? j : 0] : 0u;
+            hb[j] = j < NPF ? nhb[j < NPF ? j : 0] : 0u;
+          }
+        }
+        float dl[DW_HJ];
+        uint32_t hbits[DW_HJ];
+#pragma unroll
+        for (int j = 0; j < DW_HJ; ++j) {
+          // (the granule's pixel is column s - 1 of a row of even width: its half of the pair)
+          const int par = (((k0 + tid + DW_NTHR * j) >> 2) - 1) & 1;    // (DW_HWP is even)
+          hbits[j] = ((okm >> j) & 1u) ? (hb[j] >> (8 * (tid & 3))) & 0xffu : 0u;
+          dl[j] = head_dlogit(pr[j], bits2f((uint16_t)(tv[j] >> (16 * par))), hd_a, hd_b, p.hg.inv_total,
+                              p.hg.bce_w, hd_gs);
+        }
+        form_head_dy(k0, fl, dl, hbits);
+      }
+      // the epilogue's ReLU-mask bytes: they fly under the weight-gradient MFMAs
+      uint32_t mb[DW_BM * (BN / 8) / DW_NTHR];
+#pragma unroll
+      for (int it = 0; it < DW_BM * (BN / 8) / DW_NTHR; ++it) mb[it] = 0u;
+      if (p.mask1) epi_mask_bits_load<DW_BM, BN, DW_NTHR>(p, g0 * W, 0, tid, mb);
+      lds_barrier();        // the halo and x images are complete
+
+      wgrad_mfmas(fo);
+
+      // ---- release As and prefetch.  The mask bytes are waited for here, so that no
+      // ordinary load is outstanding while the DMA below is.
+#pragma unroll
+      for (int it = 0; it < DW_BM * (BN / 8) / DW_NTHR; ++it) asm volatile("" : "+v"(mb[it]));
+      lds_barrier();        // every wave is done reading As
+      if (win + 1 < w_end) {
+        x_dma(win + 1);
+        const int g0n = g0 + R;
+        if ((g0n % H) != 0) {                           // carried: the same image, its halo rows 2, 3
+          const bool bot_n = ((g0n + R) % H) != 0;
+          if constexpr (XF == 0) {
+            const int hr = 2 + (wave >> 1), gr = g0n - 1 + hr;
+            const bool row_ok = (hr < R + 1 || bot_n) && (unsigned)gr < (unsigned)rows_total;
+            const int rowoff = (gr - grow0) * W * C * 2;
+#pragma unroll
+            for (int i = 0; i < NPF; ++i) {
+              const int j = pj0 + i;
+              const bool ok = row_ok && j < DW_PPR && (unsigned)(16 * j + lslot - 1) < (unsigned)W;
+              nhv[i] = __builtin_amdgcn_raw_buffer_load_b128(rs1, ok ? rowoff + dma_lane + j * 1024 : OOB, 0, 0);
+            }
+          } else {
+            head_loads(g0n, true, bot_n, 2 * DW_HWP * 4, npr, ntv, nhb, nokm);
+          }
+        }
+      }
+
+      f32x4 acc[TM][TN];
+      dgrad_mfmas(acc, fo);
+      lds_barrier();        // every wave is done reading the halo image (the staging tile aliases rows 0, 1)
+      conv_epilogue<DW_BM, BN, DW_BM / 4, BN, TM, TN, DW_NTHR, EPI, StripTiles<W, RW, TC, NCS>, 0, W>(
+          p, acc, Xs + fo, g0 * W, 0, M, wave, 0, lane, tid, 0, 0, win, nullptr, HeadT{}, mb);
+    }
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);             // (nothing is prefetched past w_end)
   }
 
   // ---- sum the partials of the two waves of each dY channel block (waves jw, jw + 2:
@@ -510,14 +705,25 @@ int conv_dw_stat_rows(const ConvFwdParams& p) { return p.N * p.OH / DW_R; }
 hipError_t launch_conv_dw(const ConvFwdParams& p, hipStream_t s) {
   const int ep = conv_epi_mode(p);
   const dim3 grid(p.fw.nsplit), blk(DW_NTHR);
+  // the pipelined loop takes the epilogue's ReLU mask as preloaded bytes: a 1-bit mask (or
+  // none), no pool route; every other variant and mask form runs the serial loop
+  // (XF 4: it loads the targets and the ReLU bits as dwords)
+  const bool pipe = p.fw.pipe && (!p.mask1 || (p.mask_bits & 1)) && !p.route_gy &&
+                    (((uintptr_t)p.hg.t | (uintptr_t)p.hg.bits) & 3) == 0;
   if (p.OW > DW_W) {
     if (ep != EPI_DGRAD || p.xform || p.hg.prob) return hipErrorInvalidValue;
     UNET_LAUNCH((conv_dw_kernel<EPI_DGRAD, 0, true>), grid, blk, 0, s, p);
-  } else if (ep == EPI_DGRAD && !p.xform && !p.hg.prob)
-    UNET_LAUNCH((conv_dw_kernel<EPI_DGRAD, 0>), grid, blk, 0, s, p);
-  else if (ep == EPI_DGRAD && !p.xform)
-    UNET_LAUNCH((conv_dw_kernel<EPI_DGRAD, 4>), grid, blk, 0, s, p);
-  else if (ep == EPI_DGRAD && p.xform == 2 && !p.hg.prob)
+  } else if (ep == EPI_DGRAD && !p.xform && !p.hg.prob) {
+    if (pipe)
+      UNET_LAUNCH((conv_dw_kernel<EPI_DGRAD, 0, false, true>), grid, blk, 0, s, p);
+    else
+      UNET_LAUNCH((conv_dw_kernel<EPI_DGRAD, 0>), grid, blk, 0, s, p);
+  } else if (ep == EPI_DGRAD && !p.xform) {
+    if (pipe)
+      UNET_LAUNCH((conv_dw_kernel<EPI_DGRAD, 4, false, true>), grid, blk, 0, s, p);
+    else
+      UNET_LAUNCH((conv_dw_kernel<EPI_DGRAD, 4>), grid, blk, 0, s, p);
+  } else if (ep == EPI_DGRAD && p.xform == 2 && !p.hg.prob)
     UNET_LAUNCH((conv_dw_kernel<EPI_DGRAD, 2>), grid, blk, 0, s, p);
   else if (ep == EPI_DGRAD_NORM && !p.xform && !p.hg.prob)
     UNET_LAUNCH((conv_dw_kernel<EPI_DGRAD_NORM, 0>), grid, blk, 0, s, p);

@@ -100,6 +100,19 @@ struct StripTiles {
   }
 };
 
+// s_waitcnt immediates (gfx9 encoding: vmcnt [3:0] and [15:14], expcnt [6:4], lgkmcnt [11:8])
+// that wait for one counter only, and a workgroup barrier that waits for the wave's LDS
+// accesses alone: unlike __syncthreads() it does not drain an LDS-DMA (or any other vector
+// memory access) in flight, so a prefetch can span it.  The compiler barriers keep LDS
+// accesses from moving across it.
+constexpr int kWaitVm0 = 0x0f70, kWaitLgkm0 = 0xc07f;
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
 // Epilogue constants a persistent caller loads once (conv_win.h conv_win_pf_kernel): the
 // lane's bias values bias[j][r] (channel n0 + 16 j + 4 (lane >> 4) + r) and the fused head's
 // weights.  With them the EPI_FWD epilogue issues no global loads, so the caller's
@@ -126,19 +139,38 @@ struct HeadT {
   bool on;
 };
 
+// The EPI_DGRAD coalesced phase's ReLU-mask bytes of one tile of whole pixels (SEGW == 0,
+// one destination: D1 == Cout, 1-bit mask), thread tid's byte of chunk iteration it in
+// mb[it] -- for a caller that issues them ahead of the epilogue (conv_epilogue's pmb).
+template <int BM, int BN, int NTHR>
+__device__ __forceinline__ void epi_mask_bits_load(const ConvFwdParams& p, const int m0, const int n0, const int tid,
+                                                   uint32_t (&mb)[BM * (BN / 8) / NTHR]) {
+  constexpr int CPR = BN / 8, NIT = BM * CPR / NTHR, RPI = NTHR / CPR;
+  static_assert(BM * CPR % NTHR == 0 && NTHR % CPR == 0, "whole chunk passes");
+  const int co = n0 + (tid % CPR) * 8, ml0 = tid / CPR;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it)
+    mb[it] = ((const uint8_t*)p.mask1)[((size_t)(m0 + ml0 + it * RPI) * p.D1 + co) >> 3];
+}
+
 // SEGW > 0: the tile is a row window of SEGW-wide row segments (window kernels on rows
 // wider than one window, or any row-window kernel): tile pixel ml is at row
 // m0 + ml / SEGW (m0 = first row), column col0 + ml % SEGW of rows `pitch` pixels wide.
 // SEGW == 0: tile pixel ml is output pixel m0 + ml.
 // stat_row: this tile's row of p.stats (modes 3 / 4).  TROW > 0: the tile is BM / TROW
 // whole rows of TROW pixels (row-window kernels; enables the fused max-pool).
+// pmb (EPI_DGRAD, conv_dw.hip's pipelined loop): the tile's ReLU-mask bytes, loaded by the
+// caller with epi_mask_bits_load while an LDS-DMA prefetch of its own is in flight -- the
+// epilogue then issues no global load and its barrier waits for LDS only, so that prefetch
+// is not drained here.
 template <int BM, int BN, int WM, int WN, int TM, int TN, int NTHR, int EPI = EPI_GENERIC,
           class MapM = LinearTiles<WM>, int SEGW = 0, int TROW = 0>
 __device__ __forceinline__ HeadWsum conv_epilogue(const ConvFwdParams p, f32x4 (&acc)[TM][TN], char* smem,
                                                   const int m0, const int n0, const int M, const int wm,
                                                   const int wn, const int lane, const int tid,
                                                   const int pitch = 0, const int col0 = 0, const int stat_row = 0,
-                                                  const EpiConst<TN>* ec = nullptr, const HeadT ht = HeadT{}) {
+                                                  const EpiConst<TN>* ec = nullptr, const HeadT ht = HeadT{},
+                                                  const uint32_t* pmb = nullptr) {
   HeadWsum hws;
 #pragma unroll
   for (int k = 0; k < 3; ++k)
@@ -242,7 +274,10 @@ __device__ __forceinline__ HeadWsum conv_epilogue(const ConvFwdParams p, f32x4 (
       *(u32x2*)(E + ehalf(ml, nl)) = pk;
     }
   }
-  __syncthreads();
+  if (pmb)
+    lds_barrier();
+  else
+    __syncthreads();
 
   // coalesced phase: 16-byte chunks, consecutive threads -> consecutive channels
   constexpr int CPR = BN / 8;
@@ -399,7 +434,10 @@ __device__ __forceinline__ HeadWsum conv_epilogue(const ConvFwdParams p, f32x4 (
     const bool mbit = (p.mask_bits >> (side1 ? 0 : 1)) & 1;
     u32x4 mv[NIT];
     uint32_t mb[NIT];
-    if (mk) {
+    if (mk && pmb) {
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) mb[it] = pmb[it];
+    } else if (mk) {
 #pragma unroll
       for (int it = 0; it < NIT; ++it) {
         const int q = qof(ml0 + it * RPI);
@@ -412,7 +450,7 @@ __device__ __forceinline__ HeadWsum conv_epilogue(const ConvFwdParams p, f32x4 (
       }
     }
     // fused pool backward (route_gy, one destination; route_pix / route_hit)
-    const bool route = p.route_gy != nullptr, d3 = p.OD > 1;
+    const bool route = !pmb && p.route_gy != nullptr, d3 = p.OD > 1;
     u32x4 rg[NIT];
     uint32_t rc[NIT], rk[NIT];
     if (route) {
@@ -433,7 +471,7 @@ __device__ __forceinline__ HeadWsum conv_epilogue(const ConvFwdParams p, f32x4 (
       const int q = qof(ml);
       if (q >= M) continue;
       u32x4 v = eread(ml, cb);
-      if (mk) v = mbit ? keep_bits(v, mb[it]) : keep_pos(v, mv[it]);
+      if (mk) v = (mbit || pmb) ? keep_bits(v, mb[it]) : keep_pos(v, mv[it]);
       if (route) {
         // the (masked, 16-bit rounded) skip gradient plus the routed pool gradient,
         // in the order and precision of elementwise.hip::maxpool2_bwd_code_kernel

@@ -58,6 +58,7 @@ struct FusedWgrad {
   float* slab;                // [split_lo + nsplit rows at least][9][Cx][C1] fp32
   float* bias_slab;           // [.. rows][C1] fp32 column sums of dY (the bias gradient)
   int Cx, nsplit, split_lo;   // x channels, workgroups (slab rows) of this launch, first row
+  int pipe;                   // pipelined window loop where the variant has one (conv_dw.hip PIPE); 0: serial loop
 };
 
 // Implicit-GEMM "NT" convolution: out[q][n] = epilogue(sum_{tap,c} X[q*s + tap - pad][c] * W[n][tap][c])

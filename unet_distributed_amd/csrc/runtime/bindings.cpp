@@ -145,6 +145,7 @@ ConvFwdParams conv_params(const py::dict& d) {
   p.fw.Cx = get<int>(d, "fw_Cx", 0);
   p.fw.nsplit = get<int>(d, "fw_nsplit", 0);
   p.fw.split_lo = get<int>(d, "fw_split_lo", 0);
+  p.fw.pipe = get<int>(d, "fw_pipe", 1);
   p.xout = const_cast<void*>(getp(d, "xout"));
   p.xd_rate = get<float>(d, "xd_rate", 0.f);
   p.xd_salt = get<uint32_t>(d, "xd_salt", 0u);

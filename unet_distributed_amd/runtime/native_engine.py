@@ -78,6 +78,11 @@ def _r64(k: int) -> int:
 #   wg_target    weight-gradient split-K grid target, workgroups per gradient (512)
 #   dw_fuse      data + weight gradient of a 32 -> 32 channel conv on 128-wide rows in one kernel
 #                reading dY once (conv_dw.hip) (1)
+#   dw_pipe      fused data + weight gradient with the pipelined window loop (conv_dw.hip PIPE: the
+#                next window's x image / dY rows prefetched under the data-gradient MFMAs and
+#                epilogue, the ReLU-mask bytes loaded at the window top) on the plain and
+#                head-on-load data gradients; bit-identical results (1; 0: serial loop,
+#                profiles/r7_dw_pipe.md)
 #   dw_wgs       workgroups (= slab rows) per fused data + weight gradient launch (512)
 #   win_pf       windows per workgroup of the persistent prefetching row window on 128-wide
 #                32 -> 32 channel convs (conv_win.h conv_win_pf_kernel) (8; 0 off)
@@ -99,7 +104,7 @@ def _r64(k: int) -> int:
 ENGINE_DEFAULTS = dict(dual_stream=1, fwd_streams=2, head_fuse=1, head_onload=1, tconv_fused=2, tconv_wa=1,
                        tconv_onload=1, fwd_offset=6, wg_target=512, dw_fuse=1, dw_wgs=512, win_pf=8, win_cp=1,
                        wg_pair=0, dz_split=0, head_wsum=1, xf_drop=0, wg_pf=1, win_cp3=2, skip_onload=1,
-                       route3=1, tail3=0)
+                       route3=1, tail3=0, dw_pipe=1)
 
 
 class Fusion:
@@ -953,7 +958,7 @@ class NativeUNet:
             if d.get("route_gy") or (d.get("hg_prob") and len(parts) > 1):
                 return None       # (head-on-load: the head input's dY formed from prob / target / bits, XF 4)
             f = dict(d, rev=0, fw_x=_ptr(b[src1]) + k * half, fw_Cx=l.cin, fw_nsplit=nsplit, fw_split_lo=k * nsplit,
-                     name=d["name"])
+                     fw_pipe=self.opts["dw_pipe"], name=d["name"])
             if f.get("nz") and not self._restat_dgrad_norm(f, src1):
                 return None
             try:
