@@ -199,3 +199,24 @@ def test_persistent_window_grid():
     for other in (dict(C1=64), dict(Cout=64), dict(OW=64, IW=64, OH=64, IH=64), dict(tile=12, Cout=64)):
         d = dict(base, **other)
         assert C.conv_fwd_grid(dict(d, win_pf=8)) == C.conv_fwd_grid(d)
+
+
+def _wgrad_dict(H, M1, Nc, **kw):
+    return dict(N=2, QH=H, QW=H, AH=H, AW=H, KH=3, KW=3, pad=1, M1=M1, M2=0, Nc=Nc, a1=1, b=1, bias_mode=1, **kw)
+
+
+def test_wgrad_normalise_on_load_needs_the_32_channel_block():
+    """xform 1 (A normalised on load) exists in the prefetching 128-wide window only, which
+    has the 32-channel output block: with Nc = 64 the 64-channel block is picked and the
+    launch would reach the plain window, reading pre-norm z as the activation."""
+    C = native.require()
+    ok = _wgrad_dict(128, 32, 32, pf=1, xform=1, xa=1, xb=1)
+    C.wgrad_validate(ok)
+    with pytest.raises(ValueError):
+        C.wgrad_validate(dict(ok, Nc=64))
+
+
+def test_removed_engine_option_is_unknown():
+    from unet_distributed_amd.runtime import native_engine
+    with pytest.raises(ValueError, match="unknown"):
+        native_engine.engine_options(dict(wg_pair=1))

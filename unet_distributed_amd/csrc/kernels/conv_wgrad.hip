@@ -517,16 +517,12 @@ enum { WGEO_2D = 0, WGEO_SEG = 1, WGEO_3D = 2 };
 // HG: head-on-load (conv_params.h HeadGrad): the B operand (dY of the head input, 32
 // channels, 2D full rows) is formed per window from the head's per-pixel probability,
 // target and ReLU bits instead of being read from memory.
-// PAIR (round 6, column-unit path): wave w owns the 16-channel half jh = w & 1 of its
-// 32-channel output block, so its dW partial is 9 x 32 x 16 (72 registers instead of 144)
-// and the kernel fits three workgroups per CU (the 3D level-1 weight gradients were half
-// waits at two); the pixel splits halve and each x fragment feeds two waves.
 // DZ (xform 2, 2D single source, rows 16..64 wide): the B operand is the layer's norm
 // backward dz = ca g + cb z + cc formed on load -- p.b = g is DMA'd as usual, each thread's
 // z granules are loaded with it and the staged g image is rewritten in place (the
 // norm_bwd_apply formula and rounding; coefficients of the window's sample in LDS, Ks).
-template <int W, int QO, bool CONCAT, int GEO, bool HG = false, bool PAIR = false, bool DZ = false>
-__global__ void __launch_bounds__(NTHR, PAIR ? 3 : 2) wgrad_win_kernel(const WgradParams p) {
+template <int W, int QO, bool CONCAT, int GEO, bool HG = false, bool DZ = false>
+__global__ void __launch_bounds__(NTHR, 2) wgrad_win_kernel(const WgradParams p) {
   constexpr int BMW = 256, R = BMW / W, HR = R + 2;
   constexpr int HWP = ((W + 2 + 15) / 16) * 16, IPR = HWP / 16, ROWB = HWP * 64;
   constexpr int XI = HR * IPR, YI = QO * BMW / 16;
@@ -536,20 +532,16 @@ __global__ void __launch_bounds__(NTHR, PAIR ? 3 : 2) wgrad_win_kernel(const Wgr
   constexpr int KB = DZ ? 3 * 32 * QO * 4 : 0;         // DZ: ca / cb / cc of the block's channels
   constexpr int LDS_BYTES = (XB + YB + KB > REDB) ? XB + YB + KB : REDB;
   static_assert(W >= 8 && W <= 128 && (QO == 1 || QO == 2), "window wgrad shape");
-  static_assert(!DZ || (GEO == WGEO_2D && !HG && !PAIR && !CONCAT && W >= 16 && W <= 64 && QO == 1),
+  static_assert(!DZ || (GEO == WGEO_2D && !HG && !CONCAT && W >= 16 && W <= 64 && QO == 1),
                 "dz on load: 2D single-source full rows 16..64 wide");
   static_assert(!HG || (QO == 1 && !CONCAT && (GEO == WGEO_2D || GEO == WGEO_3D) && BMW == NTHR),
                 "head-on-load B: one 32-channel image (2D rows or 3D slices)");
-  static_assert(!PAIR || (W >= 32 && !HG), "wave-pair partials: column-unit path");
   __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
   char* Xs = smem;
   char* Ys = smem + XB;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // PAIR: wave = (ps, qo, jh) from the top bit down; pixel splits PSP = 2 / QO
-  constexpr int PSP = PAIR ? 2 / QO : PS;
-  const int jh = PAIR ? wave & 1 : 0;
-  const int qo = PAIR ? (wave >> 1) % QO : wave % QO, ps = PAIR ? (wave >> 1) / QO : wave / QO;
+  const int qo = wave % QO, ps = wave / QO;
   // Row space g = (n, d, h), rows of Wf pixels cut into nseg W-wide segments (Wf > 128);
   // a window is R rows x one segment.  3D: tap group kd (grid dimension) computes the
   // nine (dh, dw) taps of depth tap kd from the halo rows of slice d + kd - 1.
@@ -587,7 +579,7 @@ __global__ void __launch_bounds__(NTHR, PAIR ? 3 : 2) wgrad_win_kernel(const Wgr
   const bool do_bias = p.bias_mode == 1 && ci_blk == 0 && kd == (KD >> 1);
   const int gsh = (kd - (KD >> 1)) * H;
 
-  constexpr int NJ = PAIR ? 1 : 2;                      // 16-channel output halves per wave
+  constexpr int NJ = 2;                                 // 16-channel output halves per wave
   f32x4 acc[9][2][NJ];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
@@ -776,7 +768,7 @@ __global__ void __launch_bounds__(NTHR, PAIR ? 3 : 2) wgrad_win_kernel(const Wgr
       // and feeds the output rows hr - dh of all three vertical taps, so a unit reads
       // 3 (RWG + 2) A fragment pairs instead of 9 RWG.
       constexpr int NCOL = W / 32;
-      constexpr int RG = PSP > NCOL ? PSP / NCOL : 1;
+      constexpr int RG = PS > NCOL ? PS / NCOL : 1;
       constexpr int RWG = R / RG;
       constexpr int UNITS = NCOL * RG;
       static_assert(R % RG == 0 && RWG >= 1, "wgrad column units");
@@ -785,7 +777,7 @@ __global__ void __launch_bounds__(NTHR, PAIR ? 3 : 2) wgrad_win_kernel(const Wgr
       const int xsh = (CARRY && fl) ? 2 * ROWB : 0;
       const int lp = 8 * G + q;
 #pragma unroll 1
-      for (int u = ps; u < UNITS; u += PSP) {
+      for (int u = ps; u < UNITS; u += PS) {
         const int cu = u % NCOL, rr0 = (u / NCOL) * RWG;
         const int c0 = cu * 32;
         // Per-lane LDS byte bases (the swizzle depends only on lp + dw because c0 and
@@ -806,7 +798,7 @@ __global__ void __launch_bounds__(NTHR, PAIR ? 3 : 2) wgrad_win_kernel(const Wgr
 #pragma unroll
           for (int hh = 0; hh < 2; ++hh) {
             const int sl = rr0 * W + c0 + lp + 4 * hh;
-            yb[j][hh] = tr_addr(sl, sl, 16 * (PAIR ? jh : j) + 4 * pp);
+            yb[j][hh] = tr_addr(sl, sl, 16 * j + 4 * pp);
           }
         // dY fragments of the unit's rows, loaded when first needed (halo row hr = y
         // feeds output row y through dh = 0) and live for three halo rows; pixels past
@@ -946,16 +938,14 @@ __global__ void __launch_bounds__(NTHR, PAIR ? 3 : 2) wgrad_win_kernel(const Wgr
   // ---- reduce the pixel-split partials (waves with the same qo) and write the slab
   // acc[t][i][j][r] = dW[t][ci0 + 16i + 4(lane>>4) + r][co0 + 32qo + 16j + (lane&15)]
   float* red = (float*)smem;
-  const int n_base = co0 + 32 * qo + (lane & 15) + 16 * jh;
+  const int n_base = co0 + 32 * qo + (lane & 15);
   const int m_base = ci0 + 4 * (lane >> 4);
-  // (PAIR: the partner waves of (qo, jh) are ((o QO + qo) 2 + jh), o < PSP)
-  auto partner = [&](const int o) { return PAIR ? (o * QO + qo) * 2 + jh : qo + QO * o; };
   auto reduce_store = [&](const f32x4 (&v4)[2][NJ], const int t) {
     __syncthreads();
     // red[fragment (i, j)][wave * 64 + lane]: consecutive lanes 16 bytes apart (a lane-major
     // [lane][4 fragments] layout puts the 8 lanes of a 16-byte store group 64 bytes apart,
     // two 64-byte positions per 128-byte bank window: 4-way conflicted stores and loads)
-    if (PSP > 1 && ps > 0) {
+    if (PS > 1 && ps > 0) {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -969,7 +959,7 @@ __global__ void __launch_bounds__(NTHR, PAIR ? 3 : 2) wgrad_win_kernel(const Wgr
         for (int j = 0; j < NJ; ++j) {
           f32x4 v = v4[i][j];
 #pragma unroll
-          for (int o = 1; o < PSP; ++o) v += *(const f32x4*)(red + ((i * 2 + j) * NTHR + partner(o) * 64 + lane) * 4);
+          for (int o = 1; o < PS; ++o) v += *(const f32x4*)(red + ((i * 2 + j) * NTHR + (qo + QO * o) * 64 + lane) * 4);
           if (t < 9) {
             float* dst = p.slab + (((size_t)split * 9 * KD + 9 * kd + t) * Mtot + m_base + 16 * i) * p.Nc + n_base + 16 * j;
 #pragma unroll
@@ -1878,22 +1868,26 @@ __global__ void __launch_bounds__(NTHR) wgrad_s2d_win_kernel(const WgradParams p
 template <int W, int QO, int GEO>
 hipError_t launch_wgrad_win_g(const WgradParams& p, hipStream_t s) {
   const int grid = ((p.M1 + p.M2) / 32) * (p.Nc / (32 * QO)) * p.KD * launch_splits(p);
-  if constexpr ((GEO == WGEO_2D || GEO == WGEO_3D) && QO == 1) {
-    if (p.hg.prob) {
+  // one 32-channel output block on 2D full rows or 3D slices: what the head-on-load and
+  // the prefetching kernels are built for
+  constexpr bool ONE_BLOCK = QO == 1 && (GEO == WGEO_2D || GEO == WGEO_3D);
+  if (p.hg.prob) {                                      // 1. head on load: B formed per window
+    if constexpr (ONE_BLOCK) {
+      if (p.xform) return hipErrorInvalidValue;
       UNET_LAUNCH((wgrad_win_kernel<W, QO, false, GEO, true>), dim3(grid), dim3(NTHR), 0, s, p);
       return launch_status();
     }
+    return hipErrorInvalidValue;
   }
-  if (p.hg.prob) return hipErrorInvalidValue;
-  if constexpr (W == 128 && QO == 1 && (GEO == WGEO_2D || GEO == WGEO_3D)) {
-    if (p.pf && p.xform != 2 && !p.pair) {              // prefetching window (option wg_pf; xform 1: A on load)
-      if (p.xform == 1) {
-        if constexpr (GEO == WGEO_2D) {
-          UNET_LAUNCH((wgrad_pf128_kernel<false, GEO, true>), dim3(grid), dim3(NTHR), 0, s, p);
-          return launch_status();
-        }
-        return hipErrorInvalidValue;
+  if constexpr (W == 128 && ONE_BLOCK) {                // 2. prefetching window (option wg_pf)
+    if (p.pf && p.xform == 1) {                         //    xform 1: A normalised on load, 2D single source
+      if constexpr (GEO == WGEO_2D) {
+        UNET_LAUNCH((wgrad_pf128_kernel<false, GEO, true>), dim3(grid), dim3(NTHR), 0, s, p);
+        return launch_status();
       }
+      return hipErrorInvalidValue;
+    }
+    if (p.pf && !p.xform) {
       if (p.M2 > 0)
         UNET_LAUNCH((wgrad_pf128_kernel<true, GEO>), dim3(grid), dim3(NTHR), 0, s, p);
       else
@@ -1901,23 +1895,17 @@ hipError_t launch_wgrad_win_g(const WgradParams& p, hipStream_t s) {
       return launch_status();
     }
   }
-  if (p.xform == 2) {                                   // dz on load (wgrad_check: 2D single source)
+  if (p.xform == 2) {                                   // 3. dz on load (wgrad_check: 2D single source)
     if constexpr (GEO == WGEO_2D && W >= 16 && W <= 64 && QO == 1) {
       if (p.M2 > 0) return hipErrorInvalidValue;
-      UNET_LAUNCH((wgrad_win_kernel<W, QO, false, GEO, false, false, true>), dim3(grid), dim3(NTHR), 0, s, p);
+      UNET_LAUNCH((wgrad_win_kernel<W, QO, false, GEO, false, true>), dim3(grid), dim3(NTHR), 0, s, p);
       return launch_status();
     }
     return hipErrorInvalidValue;
   }
-  if constexpr (QO == 1 && W >= 32 && W <= 64) {      // (128-wide rows: 61 VGPRs spilled, 2x slower)
-    if (p.pair) {
-      if (p.M2 > 0)
-        UNET_LAUNCH((wgrad_win_kernel<W, QO, true, GEO, false, true>), dim3(grid), dim3(NTHR), 0, s, p);
-      else
-        UNET_LAUNCH((wgrad_win_kernel<W, QO, false, GEO, false, true>), dim3(grid), dim3(NTHR), 0, s, p);
-      return launch_status();
-    }
-  }
+  // 4. plain window: it applies no operand transform, so an xform 1 that reaches it (a
+  // 64-channel block, rows other than 128 wide, pf off) would read pre-norm z as the activation
+  if (p.xform) return hipErrorInvalidValue;
   if (p.M2 > 0)
     UNET_LAUNCH((wgrad_win_kernel<W, QO, true, GEO>), dim3(grid), dim3(NTHR), 0, s, p);
   else
@@ -2029,14 +2017,17 @@ const char* wgrad_check(const WgradParams& p) {
     if (KT % c.NTAP) return "wgrad: taps not divisible by the tap group";
   }
   if (p.xform != 0 && p.xform != 1 && p.xform != 2) return "wgrad: xform must be 0, 1 or 2";
+  // (Nc == 32: the prefetching window has the 32-channel output block only; the 64-channel
+  // block wgrad_pick chooses for Nc % 64 == 0 would run the plain window on pre-norm z)
   if (p.xform == 1 && (!p.pf || !wgrad_win_eligible(p) || p.QW != 128 || p.KD != 1 || p.QD != 1 || p.M2 != 0 ||
-                       p.M1 != 32 || (p.xcs != 0 && p.xcs != p.M1) || !p.xa || !p.xb || p.hg.prob || p.pair))
-    return "wgrad: A normalised on load needs the prefetching 128-wide window (2D, one 32-channel source)";
+                       p.M1 != 32 || p.Nc != 32 || (p.xcs != 0 && p.xcs != p.M1) || !p.xa || !p.xb || p.hg.prob))
+    return "wgrad: A normalised on load needs the prefetching 128-wide window (2D, one 32-channel source, 32 "
+           "output channels)";
   if (p.xform == 2 && (!p.xa || !p.xb || !p.xc || !p.xz || (p.xcs != 0 && p.xcs != p.Nc) ||
                        (wgrad_win_first_eligible(p)
                             ? (p.xcs && p.QH % ((p.QW > 256 ? p.QW : 256) / p.QW)) != 0
                             : (!wgrad_win_eligible(p) || p.KD != 1 || p.QD != 1 || p.QW < 16 || p.QW > 64 ||
-                               p.M2 != 0 || p.hg.prob || p.pair))))
+                               p.M2 != 0 || p.hg.prob))))
     return "wgrad: B transform (dz on load) needs the first-layer window wgrad or a 2D single-source row-window "
            "wgrad on rows 16..64 wide";
   if (p.upA != 1) return "wgrad: upA must be 1 (nearest upsampling is materialised)";

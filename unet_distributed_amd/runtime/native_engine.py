@@ -92,9 +92,6 @@ def _r64(k: int) -> int:
 #                gradients read: both form it on load (conv_win.h XF 2, wgrad_win_kernel DZ) (0:
 #                measured slower, r6_bench_history.md -- the consumers' per-window z loads and
 #                transform cost more than the norm_bwd_apply pass they replace)
-#   wg_pair      row-window weight gradients of 32-channel output blocks with wave-pair partials
-#                (conv_wgrad.hip wgrad_win_kernel PAIR: three workgroups per CU): 1 = 3D only,
-#                2 = 2D as well, 0 off (0)
 #   head_wsum    Mask weight gradients from the fused-head forward's sums: 1 = 2D (with head-on-load),
 #                2 = 3D as well (head_dy forms dY from the ReLU bits; measured neutral on 3D b8), 0 off (1)
 #   tail3        3D: the last data gradient in two volume halves (tail_halves) (0: measured neutral)
@@ -103,7 +100,7 @@ def _r64(k: int) -> int:
 #                -0.26 ms launch sum, +1.5..3 % 3D b8 bench, r6_bench_history.md)
 ENGINE_DEFAULTS = dict(dual_stream=1, fwd_streams=2, head_fuse=1, head_onload=1, tconv_fused=2, tconv_wa=1,
                        tconv_onload=1, fwd_offset=6, wg_target=512, dw_fuse=1, dw_wgs=512, win_pf=8, win_cp=1,
-                       wg_pair=0, dz_split=0, head_wsum=1, xf_drop=0, wg_pf=1, win_cp3=2, skip_onload=1,
+                       dz_split=0, head_wsum=1, xf_drop=0, wg_pf=1, win_cp3=2, skip_onload=1,
                        route3=1, tail3=0, dw_pipe=1)
 
 
@@ -1855,7 +1852,7 @@ class NativeUNet:
                                        "tile (its dY is never materialised for a column-sum pass)")
                 d.update(name="wgrad:" + w["lname"], M1=w["M1"], M2=w["M2"], Nc=w["Nc"], splits=splits,
                          win=self.wgrad_win, slab=slab, bias_mode=w["bias_mode"] if fused_bias else 0,
-                         bias_slab=bslab, pair=int(self.opts["wg_pair"] >= (1 if self.dims == 3 else 2)),
+                         bias_slab=bslab,
                          pf=int(self.opts["wg_pf"] >= (1 if self.dims == 3 else 2) or d.get("xform") == 1))
                 if part is not None:
                     d.update(split_lo=part * splits // 2, split_n=splits // 2)
