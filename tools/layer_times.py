@@ -75,6 +75,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--img", type=int, default=128)
     ap.add_argument("--in_channels", type=int, default=4)
+    ap.add_argument("--out_channels", type=int, default=1, help="Mask head classes (2..4: the unfused K-class head)")
     ap.add_argument("--dims", type=int, default=2)
     ap.add_argument("--upsampling", action="store_true")
     ap.add_argument("--reps", type=int, default=10)
@@ -85,12 +86,13 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     cfg = Config(batch_size=a.batch, img_size=a.img, in_channels=a.in_channels, dims=a.dims,
-                 use_upsampling=a.upsampling, norm=a.norm, groups=a.groups, dtype=a.dtype)
+                 use_upsampling=a.upsampling, norm=a.norm, groups=a.groups, dtype=a.dtype,
+                 out_channels=a.out_channels)
     spec = spec_from_config(cfg)
     flat = FlatParams(spec, device=dev)
     flat.load_dict(reference.init_params(spec, seed=1))
     e = NativeUNet(spec, flat, a.batch, a.img, dev, dtype=a.dtype)
-    x, y = synthetic_brats(min(a.batch, 64), a.img, a.in_channels, a.dims, seed=0)
+    x, y = synthetic_brats(min(a.batch, 64), a.img, a.in_channels, a.dims, seed=0, out_channels=a.out_channels)
     reps = (a.batch + 63) // 64
     x = torch.from_numpy(x).repeat((reps,) + (1,) * (x.ndim - 1))[:a.batch].to(dev)
     y = torch.from_numpy(y).repeat((reps,) + (1,) * (y.ndim - 1))[:a.batch].to(dev)
@@ -125,8 +127,9 @@ def main():
     en.record()
     torch.cuda.synchronize()
     step = st.elapsed_time(en) / a.reps
-    lines = ["# Per-launch times, native step, %dD UNet %dx%d in_ch=%d, batch %d, norm %s, %s (1x MI355X)" %
-             (a.dims, a.img, a.img, a.in_channels, a.batch, a.norm, a.dtype), "",
+    lines = ["# Per-launch times, native step, %dD UNet %dx%d in_ch=%d%s, batch %d, norm %s, %s (1x MI355X)" %
+             (a.dims, a.img, a.img, a.in_channels, " out_ch=%d" % a.out_channels if a.out_channels != 1 else "",
+              a.batch, a.norm, a.dtype), "",
              "sum of isolated launches %.3f ms; back-to-back step %.3f ms (%.0f img/s fwd+bwd only)"
              % (total, step, a.batch / step * 1e3), "",
              "| # | launch | ms | TFLOP/s |", "|---|---|---|---|"]

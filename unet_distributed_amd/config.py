@@ -166,3 +166,7 @@ def validate(cfg: Config) -> None:
         raise SystemExit("--batch_size must be positive")
     if not 0.0 <= cfg.dropout < 1.0:
         raise SystemExit("--dropout must be in [0, 1)")
+    if not 1 <= cfg.out_channels <= 4:
+        raise SystemExit("--out_channels must be 1..4")
+    if cfg.mode == 5 and cfg.out_channels > 3:
+        raise SystemExit("--mode 5 has three nested regions: --out_channels must be 1..3")

@@ -72,6 +72,25 @@ __global__ void __launch_bounds__(256) gather_batch_kernel(const float* __restri
   }
 }
 
+// gather_batch with K target channels per pixel (multi-class head, K = 2..4): y_all
+// [Nall][P][K] fp32 -> tb [B][P][K].  A pixel's K targets are 2K bytes (6 for K = 3):
+// scalar stores.  B P K < 2^31 (launcher).
+__global__ void __launch_bounds__(256) gather_batch_mc_kernel(const float* __restrict__ x_all,
+                                                              const float* __restrict__ y_all,
+                                                              const long long* __restrict__ idx, int B, int P, int Cin,
+                                                              int Cpad, int K, h16* __restrict__ xb,
+                                                              h16* __restrict__ tb) {
+  const int n = B * P;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int b = i / P;
+    const size_t s = (size_t)idx[b] * P + (i - b * P);
+    const float* src = x_all + s * Cin;
+    h16* dst = xb + (size_t)i * Cpad;
+    for (int c = 0; c < Cpad; ++c) dst[c] = (h16)(c < Cin ? src[c] : 0.f);
+    for (int k = 0; k < K; ++k) tb[(size_t)i * K + k] = (h16)y_all[s * K + k];
+  }
+}
+
 // Pooling thread map: one thread = one pooled pixel x 8 channels, 32-bit index math
 // (the 64-bit divisions of a long-long decomposition dominated these memory-bound
 // kernels).  Window corner k = (dz, dy, dx) -> input pixel base + k-offset.
@@ -468,7 +487,13 @@ hipError_t cast_input_launch(const float* x, int P, int Cin, int Cpad, void* y, 
 }
 
 hipError_t gather_batch_launch(const float* x_all, const float* y_all, const long long* idx, int B, int P, int Cin,
-                               int Cpad, void* xb, void* tb, hipStream_t s) {
+                               int Cpad, void* xb, void* tb, int K, hipStream_t s) {
+  if (K != 1) {
+    if (K < 2 || K > 4 || (long long)B * P * K >= (1LL << 31)) return hipErrorInvalidValue;
+    UNET_LAUNCH(gather_batch_mc_kernel, dim3(grid_for((long long)B * P)), dim3(256), 0, s, x_all, y_all, idx, B, P,
+                Cin, Cpad, K, (h16*)xb, (h16*)tb);
+    return launch_status();
+  }
   UNET_LAUNCH(gather_batch_kernel, dim3(grid_for((long long)B * P)), dim3(256), 0, s, x_all, y_all, idx, B, P,
                      Cin, Cpad, (h16*)xb, (h16*)tb);
   return launch_status();

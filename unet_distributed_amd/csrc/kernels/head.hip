@@ -292,6 +292,8 @@ __global__ void __launch_bounds__(256) head_grad_reduce_kernel(const float* __re
 
 }  // namespace
 
+const char* head_mc_check(int C, int K);
+
 int head_blocks(int P) {
   int nb = (P + HT - 1) / HT;
   if (nb > 1024) nb = 1024;
@@ -299,7 +301,8 @@ int head_blocks(int P) {
   return nb;
 }
 
-const char* head_check(int C) {
+const char* head_check(int C, int K) {
+  if (K != 1) return head_mc_check(C, K);      // multi-class head (head_mc.hip)
   if (C != 32 && C != 64 && C != 16) return "head: feature channels must be 16, 32 or 64";
   return nullptr;
 }

@@ -290,6 +290,8 @@ F32Wgrad f32_wgrad_params(const py::dict& d) {
   X(upsample2_fwd_launch) \
   X(head_fwd_launch) \
   X(head_bwd_launch) \
+  X(head_mc_fwd_launch) \
+  X(head_mc_bwd_launch) \
   X(head_wsum_grad_launch) \
   X(head_dy_launch) \
   X(partial_reduce_launch) \
@@ -350,14 +352,17 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
     return [=](hipStream_t s) { return A->cast_input_launch(x, a, b, c, y, s); };
   }
   if (kind == "gather_batch") {
-    // ptrs: x_all, y_all, idx (int64, device), xb, tb   ints: B, P, Cin, Cpad
+    // ptrs: x_all, y_all, idx (int64, device), xb, tb   ints: B, P, Cin, Cpad [, K target channels]
     need(5, 4, 0);
     const float *xa = (const float*)vp(0), *ya = (const float*)vp(1);
     const long long* ix = (const long long*)vp(2);
     void *xb = vp(3), *tb = vp(4);
     int B = I[0], P_ = I[1], cin = I[2], cpad = I[3];
+    const int K = I.size() > 4 ? (int)I[4] : 1;
     if (cin > cpad || cpad > 64) throw std::invalid_argument("gather_batch: Cin <= Cpad <= 64");
-    return [=](hipStream_t s) { return A->gather_batch_launch(xa, ya, ix, B, P_, cin, cpad, xb, tb, s); };
+    if (K < 1 || K > 4) throw std::invalid_argument("gather_batch: 1..4 target channels");
+    if (K > 1 && I[0] * I[1] * K >= (1LL << 31)) throw std::invalid_argument("gather_batch: B P K >= 2^31");
+    return [=](hipStream_t s) { return A->gather_batch_launch(xa, ya, ix, B, P_, cin, cpad, xb, tb, K, s); };
   }
   if (kind == "pool_fwd") {
     // ptrs: x, y[, code]
@@ -551,6 +556,12 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
     int nb = I[0], width = I[1];
     return [=](hipStream_t s) { return A->partial_reduce_launch(part, nb, width, out, s); };
   }
+  // head_fwd / head_bwd: optional third int K = output classes (absent or 1: the single-class
+  // kernels of head.hip; 2..4: head_mc.hip with w [C][K], b [K], prob / t [P][K])
+  auto head_mc_fits = [&](long long np, int C, int K) {
+    if (np * K >= (1LL << 31) || np * (C / 8) >= (1LL << 31))
+      throw std::invalid_argument("generic op '" + kind + "': P K or P C / 8 >= 2^31");
+  };
   if (kind == "head_fwd") {
     need(7, 2, 0);
     void* x = vp(0);
@@ -558,7 +569,12 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
     void* t = vp(3);
     float *prob = (float*)vp(4), *part = (float*)vp(5), *sums = (float*)vp(6);
     int P_ = I[0], C = I[1];
-    check_msg(head_check(C));
+    const int K = I.size() > 2 ? (int)I[2] : 1;
+    check_msg(head_check(C, K));
+    if (K != 1) {
+      head_mc_fits(I[0], C, K);
+      return [=](hipStream_t s) { return A->head_mc_fwd_launch(x, w, b, t, P_, C, K, prob, part, sums, s); };
+    }
     return [=](hipStream_t s) { return A->head_fwd_launch(x, w, b, t, P_, C, prob, part, sums, s); };
   }
   if (kind == "head_bwd") {
@@ -574,7 +590,15 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
     // optional 10th pointer: device float loss scale (overrides floats[2])
     const float* gsp = P.size() > 9 ? (const float*)vp(9) : nullptr;
     float it = (float)F[0], bw = (float)F[1], gs = (float)F[2];
-    check_msg(head_check(C));
+    const int K = I.size() > 2 ? (int)I[2] : 1;
+    check_msg(head_check(C, K));
+    if (K != 1) {
+      head_mc_fits(I[0], C, K);
+      if (!dx || !t) throw std::invalid_argument("head_bwd: the multi-class head writes dx and reads a target");
+      return [=](hipStream_t s) {
+        return A->head_mc_bwd_launch(x, w, prob, t, sums, P_, C, K, it, bw, gs, gsp, dx, part, gw, gb, s);
+      };
+    }
     return [=](hipStream_t s) {
       return A->head_bwd_launch(x, w, prob, t, sums, P_, C, it, bw, gs, gsp, dx, part, gw, gb, s);
     };

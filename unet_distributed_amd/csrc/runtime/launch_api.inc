@@ -22,8 +22,9 @@ hipError_t colsum_launch(const void* x, int rows, int C, int blocks, float* part
 
 hipError_t cast_input_launch(const float* x, int P, int Cin, int Cpad, void* y, hipStream_t s);
 // batch of the HBM-resident dataset by sample index -> padded 16-bit input + 16-bit target
+// (K target channels per pixel, 1..4)
 hipError_t gather_batch_launch(const float* x_all, const float* y_all, const long long* idx, int B, int P, int Cin,
-                               int Cpad, void* xb, void* tb, hipStream_t s);
+                               int Cpad, void* xb, void* tb, int K, hipStream_t s);
 // code: optional uint32 per (pooled pixel, 8 channels) = first-argmax index per channel
 // (2 / 3 bits); the backward reads it instead of x when non-null
 hipError_t maxpool2_fwd_launch(const void* x, int N, int D, int H, int W, int C, int dims3, void* y, void* code,
@@ -41,13 +42,23 @@ hipError_t upsample2_bwd_launch(const void* dup, const void* mask, int N, int D,
                                 void* dlow, hipStream_t s);
 
 int head_blocks(int P);
-const char* head_check(int C);
+const char* head_check(int C, int K = 1);     // K: output classes (1: head.hip; 2..4: head_mc.hip)
 hipError_t head_fwd_launch(const void* x, const float* w, const float* b, const void* t, int P, int C, float* prob,
                            float* partial, float* sums, hipStream_t s);
 hipError_t head_bwd_launch(const void* x, const float* w, const float* prob, const void* t, const float* sums, int P,
                            int C, float inv_total, float bce_w, float gscale, const float* gscale_ptr, void* dx,
                            float* partial, float* gw, float* gb, hipStream_t s);
 hipError_t partial_reduce_launch(const float* partial, int nb, int width, float* out, hipStream_t s);
+// multi-class head (head_mc.hip), K = 2..4 sigmoid outputs: w [C][K], b [K], prob / t [P][K];
+// partial: head_blocks(P) * max(4, C K + K) floats; hipErrorInvalidValue when P K or P C / 8
+// does not fit a 32-bit index
+const char* head_mc_check(int C, int K);
+hipError_t head_mc_fwd_launch(const void* x, const float* w, const float* b, const void* t, int P, int C, int K,
+                              float* prob, float* partial, float* sums, hipStream_t s);
+hipError_t head_mc_bwd_launch(const void* x, const float* w, const float* prob, const void* t, const float* sums,
+                              int P, int C, int K, float inv_total, float bce_w, float gscale,
+                              const float* gscale_ptr, void* dx, float* partial, float* gw, float* gb,
+                              hipStream_t s);
 // dY of the head input from its ReLU bits (no head-input read; Mask gradients from head_ws)
 hipError_t head_dy_launch(const void* bits, const float* w, const float* prob, const void* t, const float* sums, int P,
                           int C, float inv_total, float bce_w, float gscale, const float* gscale_ptr, void* dx,

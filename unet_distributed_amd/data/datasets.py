@@ -45,15 +45,35 @@ def update_channels(imgs, msks, input_no=1, output_no=1, mode=1):
         k = min(input_no, shp[3])
         new_imgs[..., :k] = imgs[..., :k]
         new_msks[..., 0] = msks[..., 0] + msks[..., 1] + msks[..., 2] + msks[..., 3]
+    elif mode == 5:                                                          # [EXT] nested regions out
+        # all modalities in (as mode 4); channel k of the mask is the region of mode 1 / 3 / 2:
+        # whole tumour, core, enhancing (output_no 1..3) -- one model with three sigmoid outputs
+        if not 1 <= output_no <= 3:
+            raise ValueError("mode 5 has three nested regions: output_no must be 1..3")
+        k = min(input_no, shp[3])
+        new_imgs[..., :k] = imgs[..., :k]
+        regions = (msks[..., 0] + msks[..., 1] + msks[..., 2] + msks[..., 3],
+                   msks[..., 0] + msks[..., 2] + msks[..., 3],
+                   msks[..., 3])
+        for c in range(output_no):
+            new_msks[..., c] = regions[c]
     else:
         new_msks[..., 0] = msks[..., 0] + msks[..., 1] + msks[..., 2] + msks[..., 3]
     return new_imgs, new_msks
 
 
+# radius scale of mask channel k of the synthetic lesions (nested regions, like BraTS's
+# whole tumour > core > enhancing)
+_NESTED_SCALE = (1.0, 0.6, 0.35, 0.2)
+
+
 def synthetic_brats(n: int, img: int = 128, channels: int = 4, dims: int = 2, seed: int = 0,
-                    dtype=np.float32, difficulty: str = "easy") -> Tuple[np.ndarray, np.ndarray]:
+                    dtype=np.float32, difficulty: str = "easy", out_channels: int = 1
+                    ) -> Tuple[np.ndarray, np.ndarray]:
     """Deterministic BraTS-like samples: [n, (img,) img, img, channels] images and
-    [n, ..., 1] binary masks.  Each sample is a smooth 'brain' disc plus 0-2
+    [n, ..., out_channels] binary masks.  Mask channel k (out_channels 1..4) is the union of
+    the same lesions' ellipsoids at radius scale (1, 0.6, 0.35, 0.2)[k] -- nested regions; the
+    random draws, the images and channel 0 do not depend on out_channels.  Each sample is a smooth 'brain' disc plus 0-2
     ellipsoidal lesions that are hyper-intense in a sample-dependent subset of
     the modalities, then z-scored per sample like `preprocess.py:117-124`.
 
@@ -65,25 +85,31 @@ def synthetic_brats(n: int, img: int = 128, channels: int = 4, dims: int = 2, se
     bright in a single modality but are NOT lesions -- a lesion bright in one modality
     and a distractor differ only in shape / size statistics, so the errors at
     boundaries and on single-modality lesions remain."""
+    if not 1 <= out_channels <= len(_NESTED_SCALE):
+        raise ValueError("synthetic data: out_channels must be 1..%d" % len(_NESTED_SCALE))
     if difficulty == "hard":
-        return _synthetic_hard(n, img, channels, dims, seed, dtype)
+        return _synthetic_hard(n, img, channels, dims, seed, dtype, out_channels)
     if difficulty != "easy":
         raise ValueError("synthetic difficulty must be easy or hard")
     rng = np.random.default_rng(seed)
     sp = (img,) * dims
     grids = np.meshgrid(*[np.linspace(-1, 1, img, dtype=np.float32)] * dims, indexing="ij")
     imgs = np.empty((n,) + sp + (channels,), dtype=dtype)
-    msks = np.zeros((n,) + sp + (1,), dtype=dtype)
+    msks = np.zeros((n,) + sp + (out_channels,), dtype=dtype)
+    inner = [np.float32(s * s) for s in _NESTED_SCALE[1:out_channels]]
     r2 = sum(g * g for g in grids)
     brain = (r2 < 0.8).astype(np.float32)
     for i in range(n):
         x = np.repeat(brain[..., None], channels, axis=-1) * (0.6 + 0.2 * rng.random(channels, dtype=np.float32))
         m = np.zeros(sp, dtype=bool)
+        mk = [np.zeros(sp, dtype=bool) for _ in inner]
         for _ in range(rng.integers(0, 3)):
             c = rng.uniform(-0.5, 0.5, size=dims).astype(np.float32)
             ax = rng.uniform(0.08, 0.3, size=dims).astype(np.float32)
             e = sum(((g - cc) / a) ** 2 for g, cc, a in zip(grids, c, ax))
             m |= e < 1.0
+            for q, s2 in zip(mk, inner):
+                q |= e < s2
         if m.any():
             gain = rng.uniform(0.5, 1.5, size=channels).astype(np.float32)
             x = x + m[..., None] * gain
@@ -91,30 +117,40 @@ def synthetic_brats(n: int, img: int = 128, channels: int = 4, dims: int = 2, se
         x = (x - x.mean()) / (x.std() + 1e-6)
         imgs[i] = x
         msks[i, ..., 0] = m
+        for k, q in enumerate(mk):
+            msks[i, ..., k + 1] = q
     return imgs, msks
 
 
-def _synthetic_hard(n, img, channels, dims, seed, dtype):
+def _synthetic_hard(n, img, channels, dims, seed, dtype, out_channels=1):
     rng = np.random.default_rng((seed, 7))
     sp = (img,) * dims
     grids = np.meshgrid(*[np.linspace(-1, 1, img, dtype=np.float32)] * dims, indexing="ij")
     px = 2.0 / img                                     # one pixel in grid units
     imgs = np.empty((n,) + sp + (channels,), dtype=dtype)
-    msks = np.zeros((n,) + sp + (1,), dtype=dtype)
+    msks = np.zeros((n,) + sp + (out_channels,), dtype=dtype)
+    inner = [np.float32(s * s) for s in _NESTED_SCALE[1:out_channels]]
     brain = (sum(g * g for g in grids) < 0.8).astype(np.float32)
 
-    def blob(radius_px):
+    def blob_e(radius_px):
         c = rng.uniform(-0.55, 0.55, size=dims).astype(np.float32)
         ax = (radius_px * px * rng.uniform(0.7, 1.3, size=dims)).astype(np.float32)
-        return sum(((g - cc) / a) ** 2 for g, cc, a in zip(grids, c, ax)) < 1.0
+        return sum(((g - cc) / a) ** 2 for g, cc, a in zip(grids, c, ax))
+
+    def blob(radius_px):
+        return blob_e(radius_px) < 1.0
 
     for i in range(n):
         base = 0.6 + 0.2 * rng.random(channels, dtype=np.float32)
         bias = 1.0 + 0.25 * sum(rng.uniform(-1, 1) * g for g in grids)       # smooth bias field
         x = (brain * bias)[..., None] * base
         m = np.zeros(sp, dtype=bool)
+        mk = [np.zeros(sp, dtype=bool) for _ in inner]
         for _ in range(rng.integers(1, 5)):
-            b = blob(rng.uniform(3.0, 7.0)) & (brain > 0)
+            e = blob_e(rng.uniform(3.0, 7.0))
+            b = (e < 1.0) & (brain > 0)
+            for q, s2 in zip(mk, inner):
+                q |= (e < s2) & (brain > 0)
             chans = rng.choice(channels, size=rng.integers(1, min(2, channels) + 1), replace=False)
             for ch in chans:
                 x[..., ch] += b * rng.uniform(0.45, 1.0) * 0.6
@@ -126,6 +162,8 @@ def _synthetic_hard(n, img, channels, dims, seed, dtype):
         x = (x - x.mean()) / (x.std() + 1e-6)
         imgs[i] = x
         msks[i, ..., 0] = m
+        for k, q in enumerate(mk):
+            msks[i, ..., k + 1] = q
     return imgs, msks
 
 

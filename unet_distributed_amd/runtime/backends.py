@@ -81,7 +81,7 @@ class TorchBackend:
     def summary_images(self, n: int) -> dict:
         """First n samples of the last training batch (channel 0; 3D: middle slice)."""
         x, t, p = self._last
-        return _summary_arrays(x, t, p, n)
+        return _summary_arrays(x, t[..., :1], p[..., :1], n)     # (several output classes: class 0)
 
     @torch.no_grad()
     def eval_sums(self, x, y) -> torch.Tensor:
@@ -109,6 +109,7 @@ class NativeBackend:
         from .f32_engine import NativeUNetF32
         self.cfg = cfg
         self.flat = flat
+        self.spec = spec
         if cfg.dtype == "fp32":
             # the reference's precision (test_dist.py:196-202): fp32 storage, fp32 MFMA
             self.engine = NativeUNetF32(spec, flat, per_rank_batch, cfg.img_size, device, loss=cfg.loss,
@@ -145,9 +146,10 @@ class NativeBackend:
         16-bit input, the target and the head's probabilities."""
         e = self.engine
         d, h, w = e.sdims(1)
-        shape = (e.B, h, w) if e.dims == 2 else (e.B, d, h, w)
+        shape = (e.B, h, w, e.K) if e.dims == 2 else (e.B, d, h, w, e.K)
         x = e.bufs["x"][..., 0]
-        return _summary_arrays(x, e.target.view(shape), e.prob.view(shape), n)
+        # (several output classes: class 0 is logged)
+        return _summary_arrays(x, e.target.view(shape)[..., 0], e.prob.view(shape)[..., 0], n)
 
     @torch.no_grad()
     def eval_sums(self, x, y) -> torch.Tensor:
@@ -161,7 +163,7 @@ class NativeBackend:
     @torch.no_grad()
     def predict(self, x) -> torch.Tensor:
         e = self.engine
-        e.load_batch(x, torch.zeros(x.shape[:-1] + (1,), device=x.device))
+        e.load_batch(x, torch.zeros(x.shape[:-1] + (self.spec.n_cl_out,), device=x.device))
         e.evaluate_batch()
         return e.probs().clone()
 
@@ -192,8 +194,15 @@ def native_supported(spec, cfg, device) -> Optional[str]:
         return "not on a GPU"
     if cfg.dtype not in ("bf16", "fp16", "fp32"):
         return "native kernels are bf16 / fp16 / fp32 (dtype=%s)" % cfg.dtype
-    if spec.n_cl_out != 1:
-        return "n_cl_out != 1"
+    if not 1 <= spec.n_cl_out <= 4:
+        return "n_cl_out=%d: the head kernels take 1..4 output classes" % spec.n_cl_out
+    if spec.n_cl_out > 1:
+        # the multi-class head (csrc/kernels/head_mc.hip) is the unfused 16-bit head
+        if spec.norm != "none":
+            return ("n_cl_out=%d with norm=%s: the normalised head kernels are single-class"
+                    % (spec.n_cl_out, spec.norm))
+        if cfg.dtype == "fp32":
+            return "n_cl_out=%d with dtype=fp32: the fp32 executor's head is single-class" % spec.n_cl_out
     if cfg.dtype == "fp32":
         # (runtime/f32_engine.py: the reference's own configuration family)
         if spec.norm != "none":

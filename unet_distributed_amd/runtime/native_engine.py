@@ -145,17 +145,21 @@ _ROW_IMGS = (16, 32, 64, 128)       # 2D images whose rows the row-window kernel
 FUSIONS: Dict[str, Fusion] = {
     "head_onload": Fusion("head input gradient formed on load by its consumers (head_grad.h)",
                           norm={"none"}, img=_ROW_IMGS, option="head_onload",
-                          when=lambda e: e.tinfo[e.head_in][1] == 32 and e.wgrad_win >= 0 and
+                          when=lambda e: e.K == 1 and e.tinfo[e.head_in][1] == 32 and e.wgrad_win >= 0 and
                           (e.dims == 2 or (e.img >= 32 and e.opts["head_onload"] >= 2))),
                           # (3D: opt-in, the column-unit window wgrad; measured 0.6 ms slower at b8 --
                           # the 3D weight gradient re-forms each depth tap's head gradient)
     "head_fuse": Fusion("Mask head in the epilogue of its input conv's forward",
-                        norm={"none"}, option="head_fuse", when=lambda e: e.tinfo[e.head_in][1] == 32),
+                        norm={"none"}, option="head_fuse",
+                        when=lambda e: e.K == 1 and e.tinfo[e.head_in][1] == 32),
     "head_wsum": Fusion("Mask weight / bias gradients from sums the head-input conv's forward accumulates "
                         "(conv_params.h head_ws): the head input is never stored -- 2D: with head-on-load, no "
                         "backward pass over it; 3D (option head_wsum=2): its dY from the ReLU bits (head_dy)",
                         norm={"none"}, option="head_wsum", needs=("head_fuse",),
-                        when=lambda e: (e.dims == 2 and e.head_onload) or (e.dims == 3 and e.opts["head_wsum"] >= 2)),
+                        when=lambda e: e.K == 1 and ((e.dims == 2 and e.head_onload) or
+                                                     (e.dims == 3 and e.opts["head_wsum"] >= 2))),
+    # (e.K == 1: the three head fusions are single-class kernels; the multi-class head, n_cl_out
+    # 2..4, runs on the standalone head_fwd / head_bwd launches of head_mc.hip)
     "pool_epilogue": Fusion("2x2 max-pool in the convNb forward epilogue", norm={"none"}),
     "fwd_2streams": Fusion("training forward as two half-batch chunks on two streams",
                            norm={"none", "group"}, even_batch=True, when=lambda e: e.opts["fwd_streams"] == 2),
@@ -218,8 +222,13 @@ class NativeUNet:
         self.opts = engine_options(opts)
         if spec.norm not in ("none", "batch", "group"):
             raise NotImplementedError("native executor: norm=%s" % spec.norm)
-        if spec.n_cl_out != 1:
-            raise NotImplementedError("native executor: n_cl_out must be 1")
+        if not 1 <= spec.n_cl_out <= 4:
+            raise NotImplementedError("native executor: n_cl_out must be 1..4")
+        if spec.n_cl_out != 1 and spec.norm != "none":
+            raise NotImplementedError("native executor: the normalised head kernels are single-class "
+                                      "(n_cl_out=%d with norm=%s)" % (spec.n_cl_out, spec.norm))
+        # output classes of the Mask head: prob / target are [pixels][K] (channels-last)
+        self.K = spec.n_cl_out
         self.spec = spec
         self.flat = flat
         self.graphs = None      # HIP-graph cache (enable_graphs)
@@ -421,7 +430,7 @@ class NativeUNet:
         # channel-padded 16-bit input; load_batch casts the fp32 batch straight into it
         # (the pad channels stay zero)
         self._buf("x", 1, self.cpad).zero_()
-        self.target = torch.zeros(self.npix(1), dtype=self.adt, device=self.device)
+        self.target = torch.zeros(self.npix(1) * self.K, dtype=self.adt, device=self.device)
         # loss-gradient scale read by the head backward (fp16 dynamic loss scaling)
         self.loss_scale_dev = torch.ones(1, dtype=torch.float32, device=self.device)
         self._loss_scale = 1.0
@@ -494,11 +503,12 @@ class NativeUNet:
                                                          device=self.device)
         self._plan_tconv_fused()
         P = self.npix(1)
-        self.prob = torch.zeros(P, dtype=torch.float32, device=self.device)
+        self.prob = torch.zeros(P * self.K, dtype=torch.float32, device=self.device)
         nb = self.C.head_blocks(P)
         self.head_nb = nb
         hc = self.tinfo[self.head_in][1]
-        self.head_partial = torch.zeros(nb * (hc + 1) + nb * 4, dtype=torch.float32, device=self.device)
+        # (head backward: per block [hc][K] weight and [K] bias partial sums)
+        self.head_partial = torch.zeros(nb * (hc + 1) * self.K + nb * 4, dtype=torch.float32, device=self.device)
         self.sums = torch.zeros(4, dtype=torch.float32, device=self.device)
         # gradient buffers: d:<tensor>, dskip:<tensor>, dfull:<tensor> (upsample fold)
         for name, (lvl, ch, _, _) in list(self.tinfo.items()):
@@ -1359,7 +1369,12 @@ class NativeUNet:
             plan.add_generic("head_fwd", [_ptr(b[self.head_in]), self.master_ptr("Mask/kernel"),
                                           self.master_ptr("Mask/bias"), _ptr(self.target),
                                           _ptr(self.prob), _ptr(part), _ptr(self.sums)],
-                             [P1, hc], [], "fwd:Mask")
+                             [P1, hc] + self._head_k(), [], "fwd:Mask")
+
+    def _head_k(self):
+        """Trailing class-count argument of the head_fwd / head_bwd / gather_batch ops: absent
+        for the single-class head (its launches are unchanged), [K] for the multi-class kernels."""
+        return [] if self.K == 1 else [self.K]
 
     def _rev_order(self, d, src, out, *also):
         """_rev_mode bit 0 (forward) / bit 1 (data gradients): a row-window conv
@@ -1454,7 +1469,7 @@ class NativeUNet:
         layers = spec.layers
         KT3 = 3 ** self.dims
         KT2 = 2 ** self.dims
-        inv_total = 1.0 / float(P1)
+        inv_total = 1.0 / float(P1 * self.K)      # BCE: the mean over every logit
 
         def emit_generic(kind, ptrs, ints, floats, name):
             ops.append(lambda pl: pl.add_generic(kind, ptrs(), ints, floats, name))
@@ -1526,7 +1541,7 @@ class NativeUNet:
                                             0 if self.head_onload else _ptr(b["d:" + self.head_in]),
                                             _ptr(self.head_partial), self.grad_ptr("Mask/kernel"),
                                             self.grad_ptr("Mask/bias"), _ptr(self.loss_scale_dev)],
-                             [P1, hc], [inv_total, self.bce_weight, 1.0],
+                             [P1, hc] + self._head_k(), [inv_total, self.bce_weight, 1.0],
                              "wgrad:Mask" if self.head_onload else "bwd:Mask")
                 done("Mask")
             elif l.kind == "conv":
@@ -1966,16 +1981,19 @@ class NativeUNet:
 
     # ------------------------------------------------------------------ running
     def load_batch(self, x: torch.Tensor, y: torch.Tensor, stream=None):
-        """x: [B, (D,) H, W, Cin] float, y: [B, (D,) H, W, 1] float/bool."""
+        """x: [B, (D,) H, W, Cin] float, y: [B, (D,) H, W, n_cl_out] float/bool."""
         cin = self.spec.in_channels
         if (x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and x.is_contiguous()
-                and y.is_contiguous() and x.shape[0] == self.B and y.numel() * cin == x.numel()):
+                and y.is_contiguous() and x.shape[0] == self.B and y.numel() * cin == x.numel() * self.K):
             # one launch: cast into the channel-padded 16-bit input and the target
             if getattr(self, "_iota", None) is None:
                 self._iota = torch.arange(self.B, device=self.device, dtype=torch.int64)
             return self.load_indexed(x, y, self._iota, stream)
         xb = self.bufs["x"].view(-1, self.cpad)
         (xb if cin == self.cpad else xb[:, :cin]).copy_(x.reshape(-1, cin), non_blocking=True)
+        if y.numel() != self.target.numel():
+            raise ValueError("target has %d elements, the executor expects %d (batch %d, %d classes)"
+                             % (y.numel(), self.target.numel(), self.B, self.K))
         self.target.copy_(y.reshape(-1), non_blocking=True)
 
     def load_indexed(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, stream=None):
@@ -1984,9 +2002,10 @@ class NativeUNet:
         cin = self.spec.in_channels
         P = x_all[0].numel() // cin
         assert idx.dtype == torch.int64 and idx.numel() == self.B and x_all.dtype == torch.float32
-        assert y_all[0].numel() == P and x_all.is_contiguous() and y_all.is_contiguous()
+        assert y_all[0].numel() == P * self.K and x_all.is_contiguous() and y_all.is_contiguous()
         self.C.generic("gather_batch", [_ptr(x_all), _ptr(y_all), _ptr(idx), _ptr(self.bufs["x"]), _ptr(self.target)],
-                       [self.B, P, cin, self.cpad], [], native.stream_handle(stream), self.dt_id)
+                       [self.B, P, cin, self.cpad] + self._head_k(), [],
+                       native.stream_handle(stream), self.dt_id)
 
     # ------------------------------------------------------------------ HIP graphs
     def enable_graphs(self):
@@ -2128,5 +2147,5 @@ class NativeUNet:
 
     def probs(self) -> torch.Tensor:
         d, h, w = self.sdims(1)
-        shape = (self.B, h, w, 1) if self.dims == 2 else (self.B, d, h, w, 1)
+        shape = (self.B, h, w, self.K) if self.dims == 2 else (self.B, d, h, w, self.K)
         return self.prob.view(shape)

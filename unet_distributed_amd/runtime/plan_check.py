@@ -83,6 +83,18 @@ def _generic_write_spans(kind: str, p: List[int], ints: List[int]) -> List[Tuple
         return [(p[5], ints[0] * ints[1] * ints[2] * 2)]
     if kind == "head_dy" and len(p) > 5 and len(ints) >= 2:
         return [(p[5], ints[0] * ints[1] * 2)]
+    # standalone head (P, C [, K classes] in ints): K-wide probabilities / Mask gradients and
+    # the per-block partial rows (head_blocks(P) = min(ceil(P / 256), 1024) rows)
+    if kind in ("head_fwd", "head_bwd") and len(ints) >= 2:
+        P, C = ints[0], ints[1]
+        K = ints[2] if len(ints) > 2 else 1
+        nb = max(1, min(-(-P // 256), 1024))
+        if kind == "head_fwd" and len(p) > 6:
+            # (loss partials: 4 floats per block; the K-class forward runs up to 2 nb blocks)
+            return [(p[4], P * K * 4), (p[5], (nb if K == 1 else 2 * nb) * 4 * 4), (p[6], 4 * 4)]
+        if kind == "head_bwd" and len(p) > 8:
+            return [(q, n) for q, n in ((p[5], P * C * 2), (p[6], nb * (C + 1) * K * 4), (p[7], C * K * 4),
+                                        (p[8], K * 4)) if q]
     return []
 
 

@@ -51,7 +51,8 @@ def main(argv=None) -> float:
     print('Loading and preprocessing test data...')
     print('-' * 38)
     if a.synthetic:
-        x, y = datasets.synthetic_brats(a.synthetic, model.img_size, model.spec.in_channels, model.spec.dims, seed=1)
+        x, y = datasets.synthetic_brats(a.synthetic, model.img_size, model.spec.in_channels, model.spec.dims, seed=1,
+                                        out_channels=model.spec.n_cl_out)
     else:
         xi, yi = datasets.load_data(a.data_path, "_test")
         x, y = datasets.update_channels(xi, yi, a.in_channels, a.out_channels, a.mode)
