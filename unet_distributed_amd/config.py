@@ -101,6 +101,7 @@ class Config:
     hip_graph: bool = True           # native: replay the forward / Adam as HIP graphs (the bench default)
     progress: bool = True
     loss_scale: float = 0.0          # fp16 static loss scale (0 = dynamic)
+    eval_threshold: float = 0.5      # probability threshold of the per-case (hard) evaluation metrics
 
     @property
     def method_up(self):
@@ -168,5 +169,7 @@ def validate(cfg: Config) -> None:
         raise SystemExit("--dropout must be in [0, 1)")
     if not 1 <= cfg.out_channels <= 4:
         raise SystemExit("--out_channels must be 1..4")
+    if not 0.0 < cfg.eval_threshold < 1.0:
+        raise SystemExit("--eval_threshold must lie strictly inside (0, 1)")
     if cfg.mode == 5 and cfg.out_channels > 3:
         raise SystemExit("--mode 5 has three nested regions: --out_channels must be 1..3")

@@ -294,6 +294,7 @@ F32Wgrad f32_wgrad_params(const py::dict& d) {
   X(head_mc_bwd_launch) \
   X(head_wsum_grad_launch) \
   X(head_dy_launch) \
+  X(seg_stats_launch) \
   X(partial_reduce_launch) \
   X(head_finish_launch) \
   X(norm_head_launch) \
@@ -623,6 +624,26 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
     const int nr = (int)I[0];
     const float it = (float)F[0], bw = (float)F[1], gs = (float)F[2];
     return [=](hipStream_t s) { return A->head_wsum_grad_launch(rows, nr, sums, it, bw, gs, gsp, gw, gb, s); };
+  }
+  if (kind == "seg_stats" || kind == "f32_seg_stats") {
+    // ptrs: prob (fp32 [N][S][K]), target ([N][S][K]; seg_stats: the 16-bit type, f32_seg_stats: fp32),
+    //       stats (fp32 [N][K][6] = {I, St, Sp, TP, FP, FN}), partial (N * seg_stats_chunks * 6 K floats;
+    //       may be 0 when seg_stats_chunks(N, S, K) is 1)
+    // ints: N samples, S pixels / voxels per sample, K classes   floats: threshold
+    need(3, 3, 1);
+    const float* prob = (const float*)vp(0);
+    const void* t = vp(1);
+    float* stats = (float*)vp(2);
+    float* part = P.size() > 3 ? (float*)vp(3) : nullptr;
+    check_msg(seg_stats_check(I[0], I[1], I[2]));
+    const int n = (int)I[0], sp = (int)I[1], K = (int)I[2];
+    const float thr = (float)F[0];
+    if (!prob || !t || !stats) throw std::invalid_argument("seg_stats: prob / target / stats required");
+    if (!part && seg_stats_chunks(n, sp, K) > 1)
+      throw std::invalid_argument("seg_stats: partial buffer required (samples are split into chunks)");
+    if (kind == "f32_seg_stats")
+      return [=](hipStream_t s) { return unet::f32_seg_stats_launch(prob, (const float*)t, n, sp, K, thr, part, stats, s); };
+    return [=](hipStream_t s) { return A->seg_stats_launch(prob, t, n, sp, K, thr, part, stats, s); };
   }
   if (kind == "norm_moments") {
     // ptrs: A, B, partial, S   ints: N, P, C    (S[n][2][C] = per-sample sums of A and A*B)
@@ -986,6 +1007,11 @@ PYBIND11_MODULE(_C, m) {
     return py::make_tuple(bm, bn);
   });
   m.def("head_blocks", &head_blocks_py);
+  // chunks per sample of a seg_stats launch: its partial buffer is N * chunks * 6 K floats
+  m.def("seg_stats_chunks", [](long long N, long long S, long long K) {
+    check_msg(seg_stats_check(N, S, K));
+    return seg_stats_chunks((int)N, (int)S, (int)K);
+  }, py::arg("N"), py::arg("S"), py::arg("K"));
   m.def("norm_blocks_per_sample", &norm_blocks_per_sample);
   m.def("sample_slices", &sample_slices);
   m.def("row_slices", &row_slices);

@@ -89,8 +89,16 @@ hipError_t head_norm_bwd_launch(const void* z, const float* prob, const void* t,
                                 int cstride, int N, int P, int C, float inv_total, float bce_w, float gscale,
                                 const float* gscale_ptr, void* dz, hipStream_t s);
 
+// per-(sample, class) evaluation statistics (seg_stats.h): prob fp32 [N][S][K], t [N][S][K] in
+// the build's 16-bit type, stats fp32 [N][K][6] = {I, St, Sp, TP, FP, FN} at threshold thr;
+// partial: N * seg_stats_chunks(N, S, K) * 6 K floats (may be null when that is one chunk)
+const char* seg_stats_check(long long N, long long S, long long K);
+int seg_stats_chunks(int N, int S, int K);
+hipError_t seg_stats_launch(const float* prob, const void* t, int N, int S, int K, float thr, float* partial,
+                            float* stats, hipStream_t s);
+
 int norm_blocks_per_sample(int N, int P);
-int sample_slices(int N);   // partial workspace of the finalize launchers: sample_slices(N) * 2 * C floats
+int sample_slices(int N);  // partial workspace of the finalize launchers: sample_slices(N) * 2 * C floats
 const char* norm_check(int C, int G);
 hipError_t norm_moments_launch(const void* A, const void* B, int N, int P, int C, float* partial, float* S,
                                hipStream_t s);
@@ -156,4 +164,7 @@ hipError_t f32_head_bwd_launch(const float* x, const float* w, const float* prob
                                float* gb, hipStream_t s);
 hipError_t f32_colsum_launch(const float* x, long long rows, int C, int blocks, float* partial, float* out,
                              hipStream_t s);
+// seg_stats with an fp32 target (f32_seg_stats.hip)
+hipError_t f32_seg_stats_launch(const float* prob, const float* t, int N, int S, int K, float thr, float* partial,
+                                float* stats, hipStream_t s);
 hipError_t f32_transpose_launch(const float* src, int T, int A, int B, int flip, float* dst, hipStream_t s);

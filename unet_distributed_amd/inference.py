@@ -80,6 +80,18 @@ class Predictor:
             outs.append(p[:m].float().cpu())
         return torch.cat(outs).numpy()
 
+    @torch.no_grad()
+    def stats(self, x, y, threshold: float = 0.5) -> np.ndarray:
+        """``[n][K][6] = {I, St, Sp, TP, FP, FN}`` per (sample, class) for any n
+        (``ops.seg_metrics``; native: chunks of ``batch``, a short last chunk padded)."""
+        x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32))
+        y = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32))
+        if self.backend.name != "native":
+            return self.backend.eval_stats(x.to(self.device), y.to(self.device), threshold).cpu().numpy()
+        outs = [self.backend.eval_stats(x[s:s + self.batch].to(self.device), y[s:s + self.batch].to(self.device),
+                                        threshold).double().cpu() for s in range(0, x.shape[0], self.batch)]
+        return torch.cat(outs).numpy()
+
 
 SIGNATURE = "intel_unet_brats_model"
 

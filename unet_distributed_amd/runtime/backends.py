@@ -8,7 +8,9 @@ gradient buffer.
   numerical oracle for the kernels).
 
 Both expose ``fwd_bwd(x, y, seed, on_segment)``, ``sums()`` (device tensor
-{I, St, Sp, BCE_sum} of the last forward) and ``eval_sums(x, y)``.
+{I, St, Sp, BCE_sum} of the last forward), ``eval_sums(x, y)`` and the per-(sample,
+class) statistics of ``ops.seg_metrics``: ``last_eval_stats(threshold)`` of the batch the
+last ``eval_sums`` scored (no second forward) and ``eval_stats(x, y, threshold)``.
 """
 
 from typing import Callable, Optional
@@ -16,7 +18,7 @@ from typing import Callable, Optional
 import torch
 
 from ..models import reference
-from ..ops import losses
+from ..ops import losses, seg_metrics
 from .params import FlatParams
 
 
@@ -88,9 +90,21 @@ class TorchBackend:
         logits = self._forward_logits(self.flat.params(), x, False, 0, self.cfg.eval_dropout).float()
         t = y.to(self.device).float()
         p = torch.sigmoid(logits)
+        self._last_eval = (t, p)
         i, st, sp = losses.dice_sums(t, p)
         bce = torch.nn.functional.binary_cross_entropy_with_logits(logits, t, reduction="sum")
         return torch.stack([i, st, sp, bce])
+
+    @torch.no_grad()
+    def last_eval_stats(self, threshold: float = 0.5) -> torch.Tensor:
+        """[n][K][6] of the batch the last ``eval_sums`` scored."""
+        t, p = self._last_eval
+        return seg_metrics.case_stats_torch(p, t, threshold)
+
+    @torch.no_grad()
+    def eval_stats(self, x, y, threshold: float = 0.5) -> torch.Tensor:
+        """[n][K][6] = {I, St, Sp, TP, FP, FN} per (sample, class) of the n samples given."""
+        return seg_metrics.case_stats_torch(self.predict(x), y.to(self.device).float(), threshold)
 
     @torch.no_grad()
     def predict(self, x) -> torch.Tensor:
@@ -159,6 +173,30 @@ class NativeBackend:
         e.load_batch(x, y)
         e.evaluate_batch()
         return e.sums.clone()
+
+    @torch.no_grad()
+    def last_eval_stats(self, threshold: float = 0.5) -> torch.Tensor:
+        """[B][K][6] of the batch the last ``eval_sums`` scored: one more launch on the
+        probabilities and target the executor still holds."""
+        return self.engine.case_stats(threshold).clone()
+
+    @torch.no_grad()
+    def eval_stats(self, x, y, threshold: float = 0.5) -> torch.Tensor:
+        """[n][K][6] = {I, St, Sp, TP, FP, FN} per (sample, class) of the n <= B samples given.
+        A short batch is zero-padded to the per-rank batch: evaluation normalises with the
+        moving BatchNorm statistics or per sample (GroupNorm), so the padding cannot change
+        a real sample's result."""
+        e = self.engine
+        n = x.shape[0]
+        if not 1 <= n <= e.B:
+            raise ValueError("native eval_stats takes 1..%d samples (the per-rank batch), got %d" % (e.B, n))
+        x, y = x.to(e.device).float(), y.to(e.device).float()
+        if n < e.B:
+            x = torch.cat([x, x.new_zeros((e.B - n,) + tuple(x.shape[1:]))])
+            y = torch.cat([y, y.new_zeros((e.B - n,) + tuple(y.shape[1:]))])
+        e.load_batch(x.contiguous(), y.contiguous())
+        e.evaluate_batch()
+        return e.case_stats(threshold)[:n].clone()
 
     @torch.no_grad()
     def predict(self, x) -> torch.Tensor:

@@ -34,6 +34,7 @@ import torch
 
 from .. import native
 from ..models.spec import UNetSpec
+from .native_engine import plan_case_stats, run_case_stats
 from .params import FlatParams
 from .plan_check import RecordingPlan
 
@@ -80,6 +81,7 @@ class NativeUNetF32:
         self.bwd_end = self.plan.size()
         self._build_forward(self.eval_plan, dropout=eval_dropout)
         self.set_buckets(bucket_bounds)
+        plan_case_stats(self, "f32_seg_stats")
         self._adam_segs()
 
     # ------------------------------------------------------------------ shapes / buffers
@@ -411,3 +413,8 @@ class NativeUNetF32:
         d, h, w = self.sdims(1)
         shape = (self.B, h, w, 1) if self.dims == 2 else (self.B, d, h, w, 1)
         return self.prob.view(shape)
+
+    def case_stats(self, threshold: float = 0.5, stream=None) -> torch.Tensor:
+        """[B][1][6] = {I, St, Sp, TP, FP, FN} per sample of the probabilities and the fp32
+        target the last forward / evaluate_batch left behind (one launch, seg_stats.h)."""
+        return run_case_stats(self, "f32_seg_stats", threshold, stream)

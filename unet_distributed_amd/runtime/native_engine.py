@@ -293,6 +293,7 @@ class NativeUNet:
         self.bwd_end = self.plan.size()
         self._build_forward(self.eval_plan, dropout=eval_dropout, train=False)
         self.set_buckets(bucket_bounds)
+        plan_case_stats(self, "seg_stats")
         if not dry_run:          # dry_run: plan construction only (CPU tests, no GPU launches)
             self.repack()
 
@@ -2149,3 +2150,42 @@ class NativeUNet:
         d, h, w = self.sdims(1)
         shape = (self.B, h, w, self.K) if self.dims == 2 else (self.B, d, h, w, self.K)
         return self.prob.view(shape)
+
+    def case_stats(self, threshold: float = 0.5, stream=None) -> torch.Tensor:
+        """[B][K][6] = {I, St, Sp, TP, FP, FN} per (sample, class) of the probabilities and
+        target the last forward / evaluate_batch left behind (one launch; the returned
+        tensor is the executor's buffer, overwritten by the next call)."""
+        return run_case_stats(self, "seg_stats", threshold, stream)
+
+
+def plan_case_stats(e, kind: str) -> None:
+    """Buffers and the validation plan of an executor's `case_stats` (kernels/seg_stats.h).
+
+    The op is not part of `plan` / `eval_plan`: `stats_plan` holds it alone (threshold 0.5)
+    so the static plan validation covers its layout and extents on a dry-run executor;
+    `run_case_stats` issues it as an immediate op with the caller's threshold."""
+    K = getattr(e, "K", 1)
+    S = e.npix(1) // e.B
+    e.case_stats_buf = e.case_stats_partial = e.stats_plan = None
+    try:
+        chunks = e.C.seg_stats_chunks(e.B, S, K)
+    except ValueError as err:               # (e.g. 2^24 voxels per sample: fp32 counts not exact)
+        e._case_stats_err = str(err)
+        return
+    e._case_stats_err = None
+    e.case_stats_buf = torch.zeros(e.B, K, 6, dtype=torch.float32, device=e.device)
+    e.case_stats_partial = torch.zeros(max(1, e.B * chunks * 6 * K), dtype=torch.float32, device=e.device)
+    e._case_stats_args = ([_ptr(e.prob), _ptr(e.target), _ptr(e.case_stats_buf), _ptr(e.case_stats_partial)],
+                          [e.B, S, K])
+    e.stats_plan = RecordingPlan(e.C.Plan(getattr(e, "dt_id", 0)))
+    e.stats_plan.add_generic(kind, e._case_stats_args[0], e._case_stats_args[1], [0.5], "case_stats")
+
+
+def run_case_stats(e, kind: str, threshold: float, stream) -> torch.Tensor:
+    if e._case_stats_err is not None:
+        raise ValueError(e._case_stats_err)
+    if e._dry:
+        raise RuntimeError("executor built with dry_run=True: case_stats is validated, not launched")
+    ptrs, ints = e._case_stats_args
+    e.C.generic(kind, ptrs, ints, [float(threshold)], native.stream_handle(stream), getattr(e, "dt_id", 0))
+    return e.case_stats_buf

@@ -95,7 +95,25 @@ def _generic_write_spans(kind: str, p: List[int], ints: List[int]) -> List[Tuple
         if kind == "head_bwd" and len(p) > 8:
             return [(q, n) for q, n in ((p[5], P * C * 2), (p[6], nb * (C + 1) * K * 4), (p[7], C * K * 4),
                                         (p[8], K * 4)) if q]
+    # per-(sample, class) statistics (N, S, K in ints): N K 6 floats of stats and one row of
+    # 6 K floats per (sample, chunk) of the partial buffer
+    if kind in ("seg_stats", "f32_seg_stats") and len(p) > 2 and len(ints) >= 3:
+        N, S, K = ints[0], ints[1], ints[2]
+        out = [(p[2], N * K * 6 * 4)]
+        chunks = seg_stats_chunks(N, S, K)
+        if len(p) > 3 and p[3] and chunks > 1:
+            out.append((p[3], N * chunks * 6 * K * 4))
+        return out
     return []
+
+
+def seg_stats_chunks(N: int, S: int, K: int) -> int:
+    """Chunks per sample of a seg_stats launch (mirrors csrc/kernels/seg_stats.hip)."""
+    it = 256 * (3 if K == 3 else 4)
+    iters = -(-(S // 8 * K) // it)
+    chunks = max(1, min(-(-1024 // N), 256, iters))
+    per = -(-iters // chunks)
+    return -(-iters // per)
 
 
 def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], List[int]]:
@@ -147,6 +165,8 @@ def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], Li
         return _sel(p, [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11]), _sel(p, [10])
     if kind == "colsum":
         return _sel(p, [0]), _sel(p, [1])
+    if kind in ("seg_stats", "f32_seg_stats"):
+        return _sel(p, [0, 1]), _sel(p, [2, 3])
     if kind == "tconv_compose":
         return _sel(p, [0, 1]), _sel(p, [2])
     if kind == "tconv_chain":
@@ -264,7 +284,7 @@ def engine_regions(e) -> Tuple[_Regions, set]:
         if k.startswith("w"):                    # bn/gn_stats workspaces (self-contained)
             inputs.add("stat:" + k)
     for k in ("prob", "target", "sums", "head_partial", "head_ws", "slab", "bias_slab", "red_stage", "arena",
-              "loss_scale_dev", "_no_dy"):
+              "loss_scale_dev", "_no_dy", "case_stats_buf", "case_stats_partial"):
         R.add(k, getattr(e, k, None))
     inputs |= {"target", "arena", "loss_scale_dev", "_no_dy"}
     for k, t in getattr(e, "state", {}).items():
@@ -288,12 +308,14 @@ def engine_regions(e) -> Tuple[_Regions, set]:
     return R, inputs
 
 
-def check_plan(e, plan, train: bool) -> List[str]:
-    """Errors of one recorded plan of executor `e` (empty list: valid)."""
+def check_plan(e, plan, train: bool, extra_inputs=()) -> List[str]:
+    """Errors of one recorded plan of executor `e` (empty list: valid).  extra_inputs: named
+    buffers an earlier plan leaves behind for this one."""
     errs = []
     for i, name, err in plan.check_dispatch(0, plan.size()):
         errs.append("op %d %s: no kernel (%s)" % (i, name, err))
     R, inputs = engine_regions(e)
+    inputs |= set(extra_inputs)
     written = set()
     for i, op in enumerate(plan.ops):
         for p in op["reads"]:
@@ -329,3 +351,11 @@ def check_plan(e, plan, train: bool) -> List[str]:
 def check_engine(e) -> Dict[str, List[str]]:
     """{'train': errors, 'eval': errors} of executor `e`'s two plans."""
     return {"train": check_plan(e, e.plan, True), "eval": check_plan(e, e.eval_plan, False)}
+
+
+def check_stats_plan(e) -> List[str]:
+    """Errors of executor `e`'s `case_stats` op (`stats_plan`): it reads the probabilities
+    the forward / evaluation plan left behind and the loaded target."""
+    if e.stats_plan is None:
+        return [e._case_stats_err]
+    return check_plan(e, e.stats_plan, False, extra_inputs=("prob",))

@@ -28,7 +28,7 @@ from ..data import datasets
 from ..data.loader import DeviceFeeder
 from ..models import reference
 from ..models.spec import spec_from_config
-from ..ops import losses
+from ..ops import losses, seg_metrics
 from ..parallel import dist as D
 from ..parallel.async_ps import AsyncPS
 from ..parallel.grad_sync import GradSync, plan_buckets
@@ -229,22 +229,55 @@ class Trainer:
     # ------------------------------------------------------------------ eval
     def evaluate(self) -> dict:
         """Per-epoch test metrics: every full per-rank batch, sharded over ranks,
-        batch metrics averaged over ALL batches (fixes the under-count of Q7)."""
+        batch metrics averaged over ALL batches (fixes the under-count of Q7).
+
+        Besides the five pooled batch metrics: `per_class` (soft Dice per class, the mean
+        over the same full batches of the per-batch value; thresholded per-case Dice,
+        sensitivity and specificity over EVERY test case, `ops.seg_metrics`), `case_dice`
+        (their mean over classes) and `cases`.  A full batch costs one more launch on the
+        forward its `eval_sums` ran; the `n % B` tail is one padded `eval_stats` call on
+        rank `nbatches % world`."""
         n = len(self.x_test)
         B = self.per_rank
         nbatches = n // B
+        K = self.spec.n_cl_out
+        thr = self.cfg.eval_threshold
         acc = torch.zeros(5, dtype=torch.float64, device=self.device)
+        # per class: sum of per-batch soft Dice | sum of case Dice | TP | FP | FN | TN; then the case count
+        cls = np.zeros(6 * K + 1, dtype=np.float64)
+
+        def hard(stats, S):
+            a = seg_metrics.accumulate(stats, S)
+            cls[K:] += np.concatenate([a["case_dice_sum"], a["tp"], a["fp"], a["fn"], a["tn"], [a["cases"]]])
+
+        def load(lo, hi):
+            return (torch.from_numpy(np.ascontiguousarray(self.x_test[lo:hi])).to(self.device),
+                    torch.from_numpy(np.ascontiguousarray(self.y_test[lo:hi])).to(self.device))
+
         for b in range(self.rank, nbatches, self.world):
-            x = torch.from_numpy(np.ascontiguousarray(self.x_test[b * B:(b + 1) * B])).to(self.device)
-            y = torch.from_numpy(np.ascontiguousarray(self.y_test[b * B:(b + 1) * B])).to(self.device)
+            x, y = load(b * B, (b + 1) * B)
             m = metrics_from_sums(self.backend.eval_sums(x, y), y.numel(), self.cfg)
             acc += torch.tensor([m["loss"], m["dice"], m["sensitivity"], m["specificity"], 1.0],
                                 dtype=torch.float64, device=self.device)
+            stats = self.backend.last_eval_stats(thr)
+            cls[:K] += seg_metrics.soft_dice(stats)
+            hard(stats, y[0].numel() // K)
+        if n % B and self.rank == nbatches % self.world:
+            x, y = load(nbatches * B, n)
+            hard(self.backend.eval_stats(x, y, thr), y[0].numel() // K)
         D.allreduce_sum_(acc)
+        cls_t = torch.from_numpy(cls).to(self.device)
+        D.allreduce_sum_(cls_t)                 # (every rank, whether or not it owns the tail)
+        cls = cls_t.cpu().numpy()
         cnt = max(acc[4].item(), 1.0)
+        hm = seg_metrics.hard_metrics({"case_dice_sum": cls[K:2 * K], "tp": cls[2 * K:3 * K], "fp": cls[3 * K:4 * K],
+                                       "fn": cls[4 * K:5 * K], "tn": cls[5 * K:6 * K], "cases": cls[6 * K]})
         return {"loss": acc[0].item() / cnt, "dice": acc[1].item() / cnt,
                 "sensitivity": acc[2].item() / cnt, "specificity": acc[3].item() / cnt,
-                "batches": int(acc[4].item())}
+                "batches": int(acc[4].item()),
+                "per_class": {"dice": [float(v) / cnt for v in cls[:K]], "case_dice": hm["case_dice"],
+                              "sensitivity": hm["sensitivity"], "specificity": hm["specificity"]},
+                "case_dice": hm["case_dice_mean"], "cases": hm["cases"]}
 
     # ------------------------------------------------------------------ step
     def _poison_due(self, step: int) -> bool:

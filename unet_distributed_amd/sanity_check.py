@@ -41,6 +41,8 @@ def main(argv=None) -> float:
     p.add_argument("--device", default=None)
     p.add_argument("--backend", default="auto", choices=["auto", "native", "torch"])
     p.add_argument("--all_batches", action="store_true")
+    p.add_argument("--per_class", action="store_true",
+                   help="also print per-class case Dice, sensitivity and specificity (thresholded at 0.5)")
     p.add_argument("--synthetic", type=int, default=0, metavar="N",
                    help="use N synthetic test slices instead of the .npy files")
     a = p.parse_args(argv)
@@ -67,6 +69,19 @@ def main(argv=None) -> float:
     dt = time.time() - t0
     avg = dice / nb if nb else float("nan")
     print("Average Dice for Test Set = {}".format(avg))
+    if a.per_class and nb:
+        # (outside the timed loop: the same samples, thresholded at 0.5)
+        from .ops import seg_metrics
+        K = model.spec.n_cl_out
+        stats = [model.stats(np.asarray(x[s:s + a.batch_size], dtype=np.float32),
+                             np.asarray(y[s:s + a.batch_size], dtype=np.float32))
+                 for s in batch_starts(len(x), a.batch_size, a.all_batches)]
+        m = seg_metrics.metrics_from_case_stats(np.concatenate(stats), int(np.prod(y.shape[1:])) // K)
+        for k in range(K):
+            print("class {}: case Dice = {}, sensitivity = {}, specificity = {}".format(
+                k, seg_metrics.fmt(m["case_dice"][k]), seg_metrics.fmt(m["sensitivity"][k]),
+                seg_metrics.fmt(m["specificity"][k])))
+        print("Case Dice = {} ({} cases)".format(seg_metrics.fmt(m["case_dice_mean"]), m["cases"]))
     print("({} batches, {} backend, {:.1f} images/sec)".format(nb, model.name, nb * a.batch_size / max(dt, 1e-9)))
     return avg
 

@@ -13,6 +13,7 @@ import json
 import sys
 import time
 
+from ..ops.seg_metrics import fmt, jsonable
 from .events import EventWriter
 
 
@@ -37,7 +38,8 @@ class MetricLogger:
 
     def _emit(self, rec):
         if self.jsonl:
-            self.jsonl.write(json.dumps(rec) + "\n")
+            # (an undefined ratio is nan: strict JSON null, never a number)
+            self.jsonl.write(json.dumps(jsonable(rec), allow_nan=False) + "\n")
             self.jsonl.flush()
 
     # TF 1.x uniquifies the second summary op of a name: the histograms the reference
@@ -69,11 +71,24 @@ class MetricLogger:
         print("\nEpoch {} of {}: TEST DATASET\nloss = {:.4f}\nDice = {:.4f}\n"
               "Sensitivity = {:.4f}\nSpecificity = {:.4f}".format(
                   epoch, epochs, m["loss"], m["dice"], m["sensitivity"], m["specificity"]), flush=True)
+        pc = m.get("per_class")
+        if pc:
+            for k in range(len(pc["dice"])):
+                print("class {}: Dice = {}, case Dice = {}, sensitivity = {}, specificity = {}".format(
+                    k, fmt(pc["dice"][k]), fmt(pc["case_dice"][k]), fmt(pc["sensitivity"][k]),
+                    fmt(pc["specificity"][k])))
+            print("Case Dice = {} ({} cases)".format(fmt(m["case_dice"]), m["cases"]), flush=True)
         self._emit(dict(kind="test_final" if final else "test", step=step, **m))
         if self.events:
             self.events.scalars(step, {"loss_test": m["loss"], "dice_test": m["dice"],
                                        "sensitivity_test": m["sensitivity"],
                                        "specificity_test": m["specificity"]})
+            if pc:
+                tags = {"case_dice_test": m["case_dice"]}
+                for k in range(len(pc["dice"])):
+                    tags["dice_test/class_%d" % k] = pc["dice"][k]
+                    tags["case_dice_test/class_%d" % k] = pc["case_dice"][k]
+                self.events.scalars(step, tags)
             self.events.flush()
 
     def close(self):
