@@ -205,7 +205,45 @@ def check_tconv_epi(W, padded=False):
     return w, r
 
 
+# ---------------------------------------------------------------- gather_aug tile transpose
+# gather_aug.h gather_aug_tile_kernel: 32 x 32 pixel tile, a pixel is nw dwords (2: Cpad 4 in
+# 16 bits; 4: Cpad 8 in 16 bits or Cpad 4 in fp32; 8: Cpad 8 in fp32), rows of 32 nw + pad
+# dwords.  Lane (r, c) = (tid >> 5, tid & 31) writes pixel [r + 8 i][c] and reads back
+# [c][r + 8 i]; 8-byte accesses for nw = 2, 16-byte pieces otherwise.  The target planes are
+# fp32 [32][33]: 4-byte accesses, same lane map.
+def read_b64(addrs):
+    return ways(addrs, 8, HALVES, 64)
+
+
+def check_gather_aug(nw, pad=None):
+    """(write ways, transposed-read ways) of the image tile."""
+    pitch = 32 * nw + ((2 if nw == 2 else 4) if pad is None else pad)
+    wr, rd = (write_b64, read_b64) if nw == 2 else (write_b128, read_b128)
+    w = r = 1
+    for wave in range(4):
+        for i in range(4):
+            lanes = [((64 * wave + l) >> 5) + 8 * i for l in range(64)]
+            for q in range(0, nw, 4 if nw > 2 else 2):
+                w = max(w, wr([4 * (lanes[l] * pitch + (l & 31) * nw + q) for l in range(64)]))
+                r = max(r, rd([4 * ((l & 31) * pitch + lanes[l] * nw + q) for l in range(64)]))
+    return w, r
+
+
+def check_gather_aug_target(pitch=33):
+    """(write ways, transposed-read ways) of one fp32 target plane."""
+    w = r = 1
+    for wave in range(4):
+        for i in range(4):
+            rows = [((64 * wave + l) >> 5) + 8 * i for l in range(64)]
+            w = max(w, ways([4 * (rows[l] * pitch + (l & 31)) for l in range(64)], 4, HALVES, 32))
+            r = max(r, ways([4 * ((l & 31) * pitch + rows[l]) for l in range(64)], 4, HALVES, 32))
+    return w, r
+
+
 if __name__ == "__main__":
+    print("gather_aug tile (write, transposed read) ways nw=2/4/8, unpadded nw=2/4:",
+          [check_gather_aug(n) for n in (2, 4, 8)], [check_gather_aug(n, 0) for n in (2, 4)],
+          "target plane:", check_gather_aug_target(), check_gather_aug_target(32))
     print("fwd b128 read/write worst ways:", check_fwd())
     for BM in (32, 64, 128, 256):
         print("tr BM=%d read/write ways:" % BM, check_tr(BM))

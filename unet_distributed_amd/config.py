@@ -102,6 +102,8 @@ class Config:
     progress: bool = True
     loss_scale: float = 0.0          # fp16 static loss scale (0 = dynamic)
     eval_threshold: float = 0.5      # probability threshold of the per-case (hard) evaluation metrics
+    augment: str = ""                # training batches only: comma-separated subset of flip, rot90, intensity
+    augment_intensity: float = 0.1   # intensity: scale in [1-a, 1+a], shift in [-a, a] per (sample, channel)
 
     @property
     def method_up(self):
@@ -124,6 +126,21 @@ _CHOICES = {
     "data_on_device": ("auto", "on", "off"),
     "synthetic_difficulty": ("easy", "hard"),
 }
+
+
+AUGMENT_NAMES = ("flip", "rot90", "intensity")
+
+
+def parse_augment(s: str) -> tuple:
+    """The --augment string as a tuple of transform names; an unknown or repeated name
+    is a SystemExit that names it."""
+    names = [t.strip() for t in str(s).split(",")] if str(s).strip() else []
+    for i, t in enumerate(names):
+        if t not in AUGMENT_NAMES:
+            raise SystemExit("--augment: unknown transform %r (choose from %s)" % (t, ", ".join(AUGMENT_NAMES)))
+        if t in names[:i]:
+            raise SystemExit("--augment: %r is listed twice" % t)
+    return tuple(names)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -171,5 +188,8 @@ def validate(cfg: Config) -> None:
         raise SystemExit("--out_channels must be 1..4")
     if not 0.0 < cfg.eval_threshold < 1.0:
         raise SystemExit("--eval_threshold must lie strictly inside (0, 1)")
+    parse_augment(cfg.augment)
+    if not 0.0 <= cfg.augment_intensity < 1.0:
+        raise SystemExit("--augment_intensity must be in [0, 1)")
     if cfg.mode == 5 and cfg.out_channels > 3:
         raise SystemExit("--mode 5 has three nested regions: --out_channels must be 1..3")

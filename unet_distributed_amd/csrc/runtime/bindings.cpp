@@ -282,6 +282,7 @@ F32Wgrad f32_wgrad_params(const py::dict& d) {
   X(colsum_launch) \
   X(cast_input_launch) \
   X(gather_batch_launch) \
+  X(gather_batch_aug_launch) \
   X(maxpool2_fwd_launch) \
   X(norm_pool_launch) \
   X(maxpool2_bwd_launch) \
@@ -364,6 +365,29 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
     if (K < 1 || K > 4) throw std::invalid_argument("gather_batch: 1..4 target channels");
     if (K > 1 && I[0] * I[1] * K >= (1LL << 31)) throw std::invalid_argument("gather_batch: B P K >= 2^31");
     return [=](hipStream_t s) { return A->gather_batch_launch(xa, ya, ix, B, P_, cin, cpad, xb, tb, K, s); };
+  }
+  if (kind == "gather_batch_aug" || kind == "f32_gather_batch_aug") {
+    // ptrs: x_all, y_all, idx (int64), code (int32 [B]), affine (fp32 [B][Cin][2] or 0), xb, tb
+    //       (gather_batch_aug: the 16-bit type, f32_gather_batch_aug: fp32)
+    // ints: B, D, H, W, Cin, Cpad, K
+    need(7, 7, 0);
+    check_msg(gather_aug_check(I[0], I[1], I[2], I[3], I[4], I[5], I[6]));
+    const float *xa = (const float*)vp(0), *ya = (const float*)vp(1);
+    const long long* ix = (const long long*)vp(2);
+    const int* code = (const int*)vp(3);
+    const float* aff = (const float*)vp(4);
+    void *xb = vp(5), *tb = vp(6);
+    if (!xa || !ya || !ix || !code || !xb || !tb)
+      throw std::invalid_argument("gather_batch_aug: x_all / y_all / idx / code / xb / tb required");
+    int B = I[0], D = I[1], H = I[2], W = I[3], cin = I[4], cpad = I[5], K = I[6];
+    if (kind == "f32_gather_batch_aug")
+      return [=](hipStream_t s) {
+        return unet::f32_gather_batch_aug_launch(xa, ya, ix, code, aff, B, D, H, W, cin, cpad, K, (float*)xb,
+                                                 (float*)tb, s);
+      };
+    return [=](hipStream_t s) {
+      return A->gather_batch_aug_launch(xa, ya, ix, code, aff, B, D, H, W, cin, cpad, K, xb, tb, s);
+    };
   }
   if (kind == "pool_fwd") {
     // ptrs: x, y[, code]

@@ -25,6 +25,14 @@ hipError_t cast_input_launch(const float* x, int P, int Cin, int Cpad, void* y, 
 // (K target channels per pixel, 1..4)
 hipError_t gather_batch_launch(const float* x_all, const float* y_all, const long long* idx, int B, int P, int Cin,
                                int Cpad, void* xb, void* tb, int K, hipStream_t s);
+// gather_batch with a per-sample geometric transform (code int32 [B]: bit 0 flip W, 1 flip H,
+// 2 swap H and W, 3 flip D) and an optional per-channel affine (fp32 [B][Cin][2] = {scale,
+// shift}, may be null) on the image (gather_aug.h); H == W
+const char* gather_aug_check(long long B, long long D, long long H, long long W, long long Cin, long long Cpad,
+                             long long K);
+hipError_t gather_batch_aug_launch(const float* x_all, const float* y_all, const long long* idx, const int* code,
+                                   const float* affine, int B, int D, int H, int W, int Cin, int Cpad, int K, void* xb,
+                                   void* tb, hipStream_t s);
 // code: optional uint32 per (pooled pixel, 8 channels) = first-argmax index per channel
 // (2 / 3 bits); the backward reads it instead of x when non-null
 hipError_t maxpool2_fwd_launch(const void* x, int N, int D, int H, int W, int C, int dims3, void* y, void* code,
@@ -167,4 +175,8 @@ hipError_t f32_colsum_launch(const float* x, long long rows, int C, int blocks, 
 // seg_stats with an fp32 target (f32_seg_stats.hip)
 hipError_t f32_seg_stats_launch(const float* prob, const float* t, int N, int S, int K, float thr, float* partial,
                                 float* stats, hipStream_t s);
+// gather_batch_aug with fp32 outputs (f32_gather_aug.hip)
+hipError_t f32_gather_batch_aug_launch(const float* x_all, const float* y_all, const long long* idx, const int* code,
+                                       const float* affine, int B, int D, int H, int W, int Cin, int Cpad, int K,
+                                       float* xb, float* tb, hipStream_t s);
 hipError_t f32_transpose_launch(const float* src, int T, int A, int B, int flip, float* dst, hipStream_t s);

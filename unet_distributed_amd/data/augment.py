@@ -1,0 +1,140 @@
+"""Training-time augmentation: random flips, 90-degree rotations and a per-channel
+brightness / contrast jitter, as per-sample parameters the batch gather applies.
+
+A sample's transform is a 4-bit code plus an optional per-input-channel affine:
+
+* bit 0 ``FW`` flip W, bit 1 ``FH`` flip H, bit 2 ``T`` swap H and W (square images),
+  bit 3 ``FD`` flip D (3D only).  Output pixel ``(d, h, w)`` reads source pixel
+  ``d' = FD ? D-1-d : d``, ``(h', w') = T ? (w, h) : (h, w)``, then ``h' = FH ? H-1-h' : h'``
+  and ``w' = FW ? W-1-w' : w'`` -- image and every target channel alike.
+* ``x' = scale * x + shift`` per (sample, input channel), image only.
+
+:func:`draw` is a counter-based hash of ``(seed, step, dataset sample index)``: a
+sample's parameters do not depend on the rank, the world size or its place in the
+batch, so data-parallel runs of any width see one augmented global batch and a resumed
+run repeats the run it resumes.  :func:`apply_torch` is the transform in plain torch
+(the ATen backend, streamed data, and the oracle of the HIP kernel
+``csrc/kernels/gather_aug.h``, which applies the same parameters inside the resident
+batch gather).
+"""
+
+from typing import Callable, Optional, Sequence, Tuple
+
+import numpy as np
+
+from ..config import parse_augment
+
+FW, FH, T, FD = 1, 2, 4, 8
+# np.rot90(m, k) of the (H, W) plane for k = 0..3 as codes
+ROT90_CODES = (0, T | FW, FH | FW, T | FH)
+
+_M64 = (1 << 64) - 1
+_GOLD = 0x9E3779B97F4A7C15
+
+
+def _mix(z: np.ndarray) -> np.ndarray:
+    """splitmix64 finaliser on uint64 arrays (wrapping arithmetic)."""
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _hash(seed: int, step: int, idx: np.ndarray, lanes: int) -> np.ndarray:
+    """uint64 [n][lanes]: independent words per (seed, step, sample index, lane)."""
+    with np.errstate(over="ignore"):
+        head = _mix(np.array([(int(seed) * _GOLD + 0x632BE59BD9B4E019) & _M64], dtype=np.uint64))
+        head = _mix(head ^ np.uint64((int(step) * _GOLD) & _M64))
+        h = _mix(head ^ (idx.astype(np.int64).view(np.uint64) * np.uint64(0xD6E8FEB86659FD93)))
+        lane = (np.arange(1, lanes + 1, dtype=np.uint64) * np.uint64(_GOLD))[None, :]
+        return _mix(h[:, None] + lane)
+
+
+def _unit(h: np.ndarray) -> np.ndarray:
+    """uint64 -> float64 in [0, 1)."""
+    return (h >> np.uint64(11)).astype(np.float64) * (1.0 / (1 << 53))
+
+
+def _f32_within(v: np.ndarray, lo: float, hi: float) -> np.ndarray:
+    """float64 in [lo, hi] -> float32 still in [lo, hi] (the rounding may step outside)."""
+    lo32, hi32 = np.float32(lo), np.float32(hi)
+    if float(lo32) < lo:
+        lo32 = np.nextafter(lo32, np.float32(np.inf))
+    if float(hi32) > hi:
+        hi32 = np.nextafter(hi32, np.float32(-np.inf))
+    return np.clip(v.astype(np.float32), lo32, hi32)
+
+
+def draw(seed: int, step: int, sample_idx, spec, cin: int, dims: int,
+         intensity: float = 0.1) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """(code int32 [n], affine float32 [n][cin][2] = {scale, shift} or None) of the dataset
+    samples `sample_idx` at global step `step`.  `spec`: the --augment string or its parsed
+    names; `intensity`: the jitter amplitude a (scale in [1-a, 1+a], shift in [-a, a])."""
+    names = parse_augment(spec) if isinstance(spec, str) else tuple(spec)
+    idx = np.asarray(sample_idx, dtype=np.int64).reshape(-1)
+    h = _hash(seed, step, idx, 1 + 2 * cin)
+    r = (h[:, 0] >> np.uint64(40)).astype(np.int64)
+    flip, rot = "flip" in names, "rot90" in names
+    if flip and rot:
+        code = r & (15 if dims == 3 else 7)
+    elif flip:
+        code = r & ((FW | FH | FD) if dims == 3 else (FW | FH))
+    elif rot:
+        code = np.asarray(ROT90_CODES, dtype=np.int64)[r & 3]
+    else:
+        code = np.zeros_like(r)
+    affine = None
+    if "intensity" in names:
+        a = float(intensity)
+        u = _unit(h[:, 1:]).reshape(len(idx), cin, 2)
+        affine = np.empty((len(idx), cin, 2), dtype=np.float32)
+        affine[..., 0] = _f32_within(1.0 - a + 2.0 * a * u[..., 0], 1.0 - a, 1.0 + a)
+        affine[..., 1] = _f32_within(-a + 2.0 * a * u[..., 1], -a, a)
+    return code.astype(np.int32), affine
+
+
+def inverse_code(code: int) -> int:
+    """The code that undoes `code` (the two quarter turns swap; every other code is an involution)."""
+    if code & T and bool(code & FH) != bool(code & FW):
+        return code ^ (FH | FW)
+    return code
+
+
+def apply_torch(x, y, code, affine=None):
+    """The transform on batch tensors x [n, (D,) H, W, C] and y [n, (D,) H, W, K] (any device):
+    new tensors, the inputs are left alone.  The affine is evaluated in float64 and rounded
+    to fp32 once."""
+    import torch
+    code = np.asarray(code.cpu() if isinstance(code, torch.Tensor) else code).reshape(-1)
+    n = x.shape[0]
+    if len(code) != n or y.shape[0] != n:
+        raise ValueError("apply_torch: %d codes for %d images and %d targets" % (len(code), n, y.shape[0]))
+    hd, wd = x.dim() - 3, x.dim() - 2
+    if x.shape[hd] != x.shape[wd] and (code & T).any():
+        raise ValueError("apply_torch: the H / W swap needs square images")
+    if x.dim() == 4 and (code & FD).any():
+        raise ValueError("apply_torch: the D flip needs 3D samples")
+    xo, yo = torch.empty_like(x), torch.empty_like(y)
+    for c in np.unique(code):
+        sel = torch.from_numpy(np.nonzero(code == c)[0]).to(x.device)
+        flips = [d for bit, d in ((FH, hd), (FW, wd), (FD, 1)) if c & bit]
+        for src, dst in ((x, xo), (y, yo)):
+            t = src.index_select(0, sel)
+            if flips:
+                t = t.flip(flips)               # the flips act on the source ...
+            if c & T:
+                t = t.transpose(hd, wd)         # ... and the swap on what they leave
+            dst.index_copy_(0, sel, t.contiguous())
+    if affine is not None:
+        af = torch.as_tensor(affine).to(x.device).double()
+        af = af.view((n,) + (1,) * (x.dim() - 2) + (af.shape[1], 2))
+        xo = (xo.double() * af[..., 0] + af[..., 1]).to(x.dtype)
+    return xo, yo
+
+
+def make_aug(cfg, step: int) -> Optional[Callable[[Sequence[int]], Tuple[np.ndarray, Optional[np.ndarray]]]]:
+    """The per-step callable a DeviceFeeder takes (dataset sample indices -> parameters),
+    or None when --augment is off."""
+    names = parse_augment(cfg.augment)
+    if not names:
+        return None
+    return lambda idx: draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity)

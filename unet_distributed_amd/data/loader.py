@@ -11,6 +11,8 @@ for sequential reads.  ``--num_threads`` (README.md:63) sizes the gather pool.
 import numpy as np
 import torch
 
+from .augment import apply_torch
+
 
 class BatchLoader:
     def __init__(self, x: np.ndarray, y: np.ndarray, per_rank: int, threads: int = 8, pin: bool = False):
@@ -46,13 +48,18 @@ class BatchLoader:
 class ResidentBatch:
     """A batch of the HBM-resident dataset named by sample index: the native backend
     gathers and casts it into its input buffers in one kernel; anything else asks
-    for the tensors."""
+    for the tensors.  `aug`: optional augmentation parameters of the batch on the
+    device, (code int32 [n], affine float32 [n][Cin][2] or None) (data/augment.py)."""
 
-    def __init__(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor):
+    def __init__(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, aug=None):
         self.x_all, self.y_all, self.idx = x_all, y_all, idx
+        self.aug = aug
 
     def tensors(self):
-        return self.x_all.index_select(0, self.idx), self.y_all.index_select(0, self.idx)
+        x, y = self.x_all.index_select(0, self.idx), self.y_all.index_select(0, self.idx)
+        if self.aug is not None:
+            x, y = apply_torch(x, y, *self.aug)
+        return x, y
 
     @property
     def npix(self) -> int:
@@ -94,9 +101,36 @@ class DeviceFeeder:
         self.events = [None] * len(self.loaders)
         self.k = 0
 
-    def get(self, idx: np.ndarray, lazy: bool = False):
+    def _upload(self, sorted_idx: np.ndarray, code: np.ndarray, affine):
+        """Index tensor and augmentation parameters in one small non-blocking copy:
+        [idx int64 | affine fp32 | code int32] -> (idx, (code, affine)) device views."""
+        n = len(sorted_idx)
+        af = np.ascontiguousarray(affine, dtype=np.float32) if affine is not None else np.empty(0, np.float32)
+        parts = [sorted_idx.view(np.uint8), af.reshape(-1).view(np.uint8),
+                 np.ascontiguousarray(code, dtype=np.int32).view(np.uint8)]
+        buf = torch.from_numpy(np.concatenate(parts)).to(self.device, non_blocking=True)
+        na = parts[1].size
+        ii = buf[:8 * n].view(torch.int64)
+        af = buf[8 * n:8 * n + na].view(torch.float32).view(affine.shape) if affine is not None else None
+        return ii, (buf[8 * n + na:].view(torch.int32), af)
+
+    def get(self, idx: np.ndarray, lazy: bool = False, aug=None):
         """(x, y) of the samples `idx`; lazy (resident data only): a ResidentBatch
-        for a backend that gathers it itself."""
+        for a backend that gathers it itself.  `aug`: optional callable, sorted dataset
+        sample indices -> (code, affine) (data/augment.py): the batch is augmented with
+        them (a ResidentBatch carries them for the backend's gather kernel)."""
+        if aug is None:
+            return self._get(idx, lazy)
+        si = np.sort(np.asarray(idx, dtype=np.int64))       # (the order every path below feeds)
+        code, affine = aug(si)
+        if self.resident:
+            ii, dev = self._upload(si, code, affine)
+            if lazy:
+                return ResidentBatch(self.x, self.y, ii, dev), None
+            return apply_torch(self.x.index_select(0, ii), self.y.index_select(0, ii), code, affine)
+        return apply_torch(*self._get(idx, False), code, affine)
+
+    def _get(self, idx: np.ndarray, lazy: bool):
         if self.resident:
             ii = torch.from_numpy(np.sort(np.asarray(idx, dtype=np.int64))).to(self.device, non_blocking=True)
             if lazy:

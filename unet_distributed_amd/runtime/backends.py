@@ -146,7 +146,10 @@ class NativeBackend:
         e = self.engine
         e.set_loss_scale(grad_scale)
         if hasattr(x, "x_all"):
-            e.load_indexed(x.x_all, x.y_all, x.idx)
+            if getattr(x, "aug", None) is not None:
+                e.load_indexed(x.x_all, x.y_all, x.idx, aug=x.aug)
+            else:
+                e.load_indexed(x.x_all, x.y_all, x.idx)
         else:
             e.load_batch(x, y)
         e.forward(seed)

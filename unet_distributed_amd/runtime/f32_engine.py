@@ -34,7 +34,7 @@ import torch
 
 from .. import native
 from ..models.spec import UNetSpec
-from .native_engine import plan_case_stats, run_case_stats
+from .native_engine import gather_aug_args, plan_case_stats, run_case_stats
 from .params import FlatParams
 from .plan_check import RecordingPlan
 
@@ -380,7 +380,19 @@ class NativeUNetF32:
         self.bufs["x"].view(-1).copy_(x.reshape(-1), non_blocking=True)
         self.target.copy_(y.reshape(-1), non_blocking=True)
 
-    def load_indexed(self, x_all, y_all, idx, stream=None):
+    def load_indexed(self, x_all, y_all, idx, stream=None, aug=None):
+        """`aug`: optional (code, affine) on the device (data/augment.py): one
+        f32_gather_batch_aug launch gathers and transforms the batch (kernels/gather_aug.h)."""
+        if aug is not None:
+            cin = self.spec.in_channels
+            K = y_all[0].numel() * cin // x_all[0].numel()
+            assert idx.dtype == torch.int64 and idx.numel() == self.B and x_all.dtype == torch.float32
+            assert y_all.dtype == torch.float32 and x_all.is_contiguous() and y_all.is_contiguous()
+            assert self.bufs["x"].numel() == self.B * x_all[0].numel()
+            assert self.target.numel() == self.B * y_all[0].numel()
+            ptrs, ints = gather_aug_args(self, x_all, y_all, idx, aug, cin, cin, K)
+            self.C.generic("f32_gather_batch_aug", ptrs, ints, [], native.stream_handle(stream), 0)
+            return
         self.bufs["x"].copy_(x_all.index_select(0, idx).view_as(self.bufs["x"]))
         self.target.copy_(y_all.index_select(0, idx).reshape(-1))
 

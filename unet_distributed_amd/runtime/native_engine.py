@@ -1997,13 +1997,20 @@ class NativeUNet:
                              % (y.numel(), self.target.numel(), self.B, self.K))
         self.target.copy_(y.reshape(-1), non_blocking=True)
 
-    def load_indexed(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, stream=None):
+    def load_indexed(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, stream=None, aug=None):
         """Batch = samples `idx` (device int64) of the HBM-resident dataset, gathered
-        and cast straight into the padded 16-bit input and target (one launch)."""
+        and cast straight into the padded 16-bit input and target (one launch).  `aug`:
+        optional (code int32 [B], affine float32 [B][Cin][2] or None) on the device
+        (data/augment.py): the same launch flips / rotates each sample and applies its
+        per-channel affine (kernels/gather_aug.h)."""
         cin = self.spec.in_channels
         P = x_all[0].numel() // cin
         assert idx.dtype == torch.int64 and idx.numel() == self.B and x_all.dtype == torch.float32
         assert y_all[0].numel() == P * self.K and x_all.is_contiguous() and y_all.is_contiguous()
+        if aug is not None:
+            ptrs, ints = gather_aug_args(self, x_all, y_all, idx, aug, cin, self.cpad, self.K)
+            self.C.generic("gather_batch_aug", ptrs, ints, [], native.stream_handle(stream), self.dt_id)
+            return
         self.C.generic("gather_batch", [_ptr(x_all), _ptr(y_all), _ptr(idx), _ptr(self.bufs["x"]), _ptr(self.target)],
                        [self.B, P, cin, self.cpad] + self._head_k(), [],
                        native.stream_handle(stream), self.dt_id)
@@ -2156,6 +2163,23 @@ class NativeUNet:
         target the last forward / evaluate_batch left behind (one launch; the returned
         tensor is the executor's buffer, overwritten by the next call)."""
         return run_case_stats(self, "seg_stats", threshold, stream)
+
+
+def gather_aug_args(e, x_all, y_all, idx, aug, cin: int, cpad: int, K: int):
+    """(ptrs, ints) of an executor's gather_batch_aug / f32_gather_batch_aug launch
+    (bindings.cpp) from the resident dataset [N, (D,) H, W, Cin] and `aug` = (code, affine)."""
+    code, affine = aug
+    D = x_all.shape[1] if x_all.dim() == 5 else 1
+    H, W = x_all.shape[-3], x_all.shape[-2]
+    if code.dtype != torch.int32 or code.numel() != e.B or code.device != x_all.device or not code.is_contiguous():
+        raise ValueError("augmentation codes: a contiguous int32 [%d] tensor on %s" % (e.B, x_all.device))
+    if affine is not None and (affine.dtype != torch.float32 or tuple(affine.shape) != (e.B, cin, 2)
+                               or affine.device != x_all.device or not affine.is_contiguous()):
+        raise ValueError("augmentation affine: a contiguous float32 [%d][%d][2] tensor on %s"
+                         % (e.B, cin, x_all.device))
+    ptrs = [_ptr(x_all), _ptr(y_all), _ptr(idx), _ptr(code), _ptr(affine) if affine is not None else 0,
+            _ptr(e.bufs["x"]), _ptr(e.target)]
+    return ptrs, [e.B, D, H, W, cin, cpad, K]
 
 
 def plan_case_stats(e, kind: str) -> None:

@@ -104,6 +104,12 @@ def _generic_write_spans(kind: str, p: List[int], ints: List[int]) -> List[Tuple
         if len(p) > 3 and p[3] and chunks > 1:
             out.append((p[3], N * chunks * 6 * K * 4))
         return out
+    # augmenting batch gather (B, D, H, W, Cin, Cpad, K in ints): the padded input and the target,
+    # 16-bit (gather_batch_aug) or fp32 (f32_gather_batch_aug)
+    if kind in ("gather_batch_aug", "f32_gather_batch_aug") and len(p) > 6 and len(ints) >= 7:
+        B, D, H, W, _, cpad, K = ints[:7]
+        eb = 4 if kind.startswith("f32") else 2
+        return [(p[5], B * D * H * W * cpad * eb), (p[6], B * D * H * W * K * eb)]
     return []
 
 
@@ -167,6 +173,8 @@ def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], Li
         return _sel(p, [0]), _sel(p, [1])
     if kind in ("seg_stats", "f32_seg_stats"):
         return _sel(p, [0, 1]), _sel(p, [2, 3])
+    if kind in ("gather_batch_aug", "f32_gather_batch_aug"):
+        return [q for q in _sel(p, [0, 1, 2, 3, 4]) if q], _sel(p, [5, 6])
     if kind == "tconv_compose":
         return _sel(p, [0, 1]), _sel(p, [2])
     if kind == "tconv_chain":

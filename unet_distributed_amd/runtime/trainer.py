@@ -24,7 +24,9 @@ import numpy as np
 import torch
 
 from .. import settings
+from ..config import parse_augment
 from ..data import datasets
+from ..data.augment import make_aug
 from ..data.loader import DeviceFeeder
 from ..models import reference
 from ..models.spec import spec_from_config
@@ -220,11 +222,19 @@ class Trainer:
         if self.is_chief:
             print("Training data: %s" % ("resident in device memory" if self.feeder.resident
                                          else "streamed from host (pinned, double-buffered)"))
+            if cfg.augment:
+                names = parse_augment(cfg.augment)
+                print("Training augmentation: %s%s" % (", ".join(names), " (amplitude %g)" % cfg.augment_intensity
+                                                       if "intensity" in names else ""))
 
-    def _batch(self, idx: np.ndarray):
+    def _batch(self, idx: np.ndarray, step: int = 0):
         # native backend + resident data: the backend gathers the batch itself (one
         # gather+cast kernel into its input buffers, no fp32 batch copy)
-        return self.feeder.get(idx, lazy=self.backend.name == "native")
+        lazy = self.backend.name == "native"
+        if not self.cfg.augment:
+            return self.feeder.get(idx, lazy=lazy)
+        # --augment: per-sample parameters from (seed, step, dataset index) ride on the gather
+        return self.feeder.get(idx, lazy=lazy, aug=make_aug(self.cfg, step))
 
     # ------------------------------------------------------------------ eval
     def evaluate(self) -> dict:
@@ -372,7 +382,7 @@ class Trainer:
             if batch_idx == 0 and step // self.num_batches != epoch:
                 epoch = step // self.num_batches
                 epoch_idx = self.sampler.epoch_indices(epoch)     # reshuffle (test_dist.py:449-452)
-            x, y = self._batch(epoch_idx[batch_idx])
+            x, y = self._batch(epoch_idx[batch_idx], step)
             if cfg.fault_inject_step >= 0 and step == cfg.fault_inject_step and \
                     (cfg.fault_inject_rank < 0 or cfg.fault_inject_rank == self.rank):
                 raise FaultInjected("fault injected at step %d on rank %d" % (step, self.rank))
