@@ -102,6 +102,7 @@ class Config:
     progress: bool = True
     loss_scale: float = 0.0          # fp16 static loss scale (0 = dynamic)
     eval_threshold: float = 0.5      # probability threshold of the per-case (hard) evaluation metrics
+    eval_hd95: bool = False          # evaluation also reports the per-case 95th-percentile Hausdorff distance
     augment: str = ""                # training batches only: comma-separated subset of flip, rot90, intensity
     augment_intensity: float = 0.1   # intensity: scale in [1-a, 1+a], shift in [-a, a] per (sample, channel)
 

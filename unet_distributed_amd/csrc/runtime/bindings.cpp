@@ -296,6 +296,7 @@ F32Wgrad f32_wgrad_params(const py::dict& d) {
   X(head_wsum_grad_launch) \
   X(head_dy_launch) \
   X(seg_stats_launch) \
+  X(surf_dist_launch) \
   X(partial_reduce_launch) \
   X(head_finish_launch) \
   X(norm_head_launch) \
@@ -669,6 +670,27 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
       return [=](hipStream_t s) { return unet::f32_seg_stats_launch(prob, (const float*)t, n, sp, K, thr, part, stats, s); };
     return [=](hipStream_t s) { return A->seg_stats_launch(prob, t, n, sp, K, thr, part, stats, s); };
   }
+  if (kind == "surf_dist" || kind == "f32_surf_dist") {
+    // ptrs: prob (fp32 [N][S][K]), target ([N][S][K]; surf_dist: the 16-bit type, f32_surf_dist: fp32),
+    //       surf (int32 [N][K][4] = {mp, mt, q_lo, q_hi}), scratch (surf_dist_scratch(N, D, H, W, K) bytes,
+    //       16-byte aligned)
+    // ints: N samples, D, H, W (D = 1: 2D), K classes   floats: threshold
+    need(4, 5, 1);
+    const float* prob = (const float*)vp(0);
+    const void* t = vp(1);
+    int* surf = (int*)vp(2);
+    int* field = (int*)vp(3);
+    check_msg(surf_dist_check(I[0], I[1], I[2], I[3], I[4]));
+    const int n = (int)I[0], d = (int)I[1], h = (int)I[2], w = (int)I[3], K = (int)I[4];
+    const float thr = (float)F[0];
+    if (!prob || !t || !surf) throw std::invalid_argument("surf_dist: prob / target / surf required");
+    if (!field || (P[3] & 15)) throw std::invalid_argument("surf_dist: 16-byte aligned scratch buffer required");
+    if (kind == "f32_surf_dist")
+      return [=](hipStream_t s) {
+        return unet::f32_surf_dist_launch(prob, (const float*)t, n, d, h, w, K, thr, field, surf, s);
+      };
+    return [=](hipStream_t s) { return A->surf_dist_launch(prob, t, n, d, h, w, K, thr, field, surf, s); };
+  }
   if (kind == "norm_moments") {
     // ptrs: A, B, partial, S   ints: N, P, C    (S[n][2][C] = per-sample sums of A and A*B)
     need(4, 3, 0);
@@ -1036,6 +1058,11 @@ PYBIND11_MODULE(_C, m) {
     check_msg(seg_stats_check(N, S, K));
     return seg_stats_chunks((int)N, (int)S, (int)K);
   }, py::arg("N"), py::arg("S"), py::arg("K"));
+  // bytes of the scratch of a surf_dist launch over N samples (int32 fields [N][K][2][S])
+  m.def("surf_dist_scratch", [](long long N, long long D, long long H, long long W, long long K) {
+    check_msg(surf_dist_check(N, D, H, W, K));
+    return surf_dist_scratch(N, D, H, W, K);
+  }, py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("K"));
   m.def("norm_blocks_per_sample", &norm_blocks_per_sample);
   m.def("sample_slices", &sample_slices);
   m.def("row_slices", &row_slices);

@@ -105,6 +105,14 @@ int seg_stats_chunks(int N, int S, int K);
 hipError_t seg_stats_launch(const float* prob, const void* t, int N, int S, int K, float thr, float* partial,
                             float* stats, hipStream_t s);
 
+// surface distances for HD95 (surf_dist.h): prob fp32 [N][S][K], t [N][S][K] in the build's 16-bit
+// type, S = D H W; surf int32 [N][K][4] = {mp, mt, q_lo, q_hi} at threshold thr; field: scratch of
+// surf_dist_scratch(N, D, H, W, K) bytes, 16-byte aligned, written before it is read
+const char* surf_dist_check(long long N, long long D, long long H, long long W, long long K);
+long long surf_dist_scratch(long long N, long long D, long long H, long long W, long long K);
+hipError_t surf_dist_launch(const float* prob, const void* t, int N, int D, int H, int W, int K, float thr, int* field,
+                            int* surf, hipStream_t s);
+
 int norm_blocks_per_sample(int N, int P);
 int sample_slices(int N);  // partial workspace of the finalize launchers: sample_slices(N) * 2 * C floats
 const char* norm_check(int C, int G);
@@ -179,4 +187,7 @@ hipError_t f32_seg_stats_launch(const float* prob, const float* t, int N, int S,
 hipError_t f32_gather_batch_aug_launch(const float* x_all, const float* y_all, const long long* idx, const int* code,
                                        const float* affine, int B, int D, int H, int W, int Cin, int Cpad, int K,
                                        float* xb, float* tb, hipStream_t s);
+// surf_dist with an fp32 target (f32_surf_dist.hip)
+hipError_t f32_surf_dist_launch(const float* prob, const float* t, int N, int D, int H, int W, int K, float thr,
+                                int* field, int* surf, hipStream_t s);
 hipError_t f32_transpose_launch(const float* src, int T, int A, int B, int flip, float* dst, hipStream_t s);

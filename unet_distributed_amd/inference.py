@@ -92,6 +92,18 @@ class Predictor:
                                         threshold).double().cpu() for s in range(0, x.shape[0], self.batch)]
         return torch.cat(outs).numpy()
 
+    @torch.no_grad()
+    def surface(self, x, y, threshold: float = 0.5) -> np.ndarray:
+        """int64 ``[n][K][4] = {mp, mt, q_lo, q_hi}`` per (sample, class) for any n: the
+        surface-distance integers of HD95 (``ops.seg_metrics.hd95_from_surface``; native:
+        chunks of ``batch``, a short last chunk padded)."""
+        x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32))
+        y = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32))
+        step = self.batch if self.backend.name == "native" else max(1, x.shape[0])
+        outs = [self.backend.eval_surface(x[s:s + step].to(self.device), y[s:s + step].to(self.device),
+                                          threshold).long().cpu() for s in range(0, x.shape[0], step)]
+        return torch.cat(outs).numpy()
+
 
 SIGNATURE = "intel_unet_brats_model"
 

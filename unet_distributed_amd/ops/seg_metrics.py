@@ -110,6 +110,128 @@ def metrics_from_case_stats(stats, S: int, valid=None) -> dict:
     return m
 
 
+# ---------------------------------------------------------------------------------------
+# 95th-percentile Hausdorff distance (HD95)
+#
+# ``surf[n][k] = {mp, mt, q_lo, q_hi}`` of sample n and class k, on the sample's grid (H x W,
+# or D x H x W; unit spacing, distances in voxels): with P = {p >= float32(thr)} and
+# T = {t >= 0.5}, the surface of a mask is its voxels with a face neighbour (4 in 2D, 6 in
+# 3D) outside the mask, a neighbour outside the grid counting as outside the mask
+# (``A & ~binary_erosion(A)`` with scipy's defaults).  ``mp`` and ``mt`` are the surface sizes.
+# Q is the multiset of squared distances from every surface voxel of P to the surface of T
+# and the reverse, ``m = mp + mt``, ``r = 95 (m - 1)``, ``lo = r // 100``,
+# ``hi = min(lo + 1, m - 1)``: ``q_lo`` and ``q_hi`` are the elements of rank lo and hi of
+# sorted Q, or -1 when a surface is empty.  Then
+# ``hd95 = sqrt(q_lo) + (r % 100) / 100 * (sqrt(q_hi) - sqrt(q_lo))``, which is
+# ``numpy.percentile(hstack(d_PT, d_TP), 95)`` (the MedPy convention).  Both surfaces empty
+# score 0.0; exactly one empty scores the grid diagonal ``sqrt(D^2 + H^2 + W^2)``, D = 1 in 2D.  The native executors produce the
+# integers with the separable distance transform of ``csrc/kernels/surf_dist.h``;
+# :func:`case_surface_torch` finds them from all pairs of surface voxels.
+
+NSURF = 4
+_PAIR_CHUNK = 1 << 22           # distances formed at a time by the all-pairs oracle
+
+
+def _grid_of(shape) -> tuple:
+    g = tuple(int(v) for v in shape)
+    if len(g) == 3 and g[0] == 1:           # (a one-slice volume is a 2D grid)
+        g = g[1:]
+    if len(g) not in (2, 3):
+        raise ValueError("a sample grid is (H, W) or (D, H, W), got %s" % (tuple(shape),))
+    return g
+
+
+def _surface(mask: torch.Tensor) -> torch.Tensor:
+    """Voxels of the boolean ``mask`` (one sample's grid) with a face neighbour outside it."""
+    inner = mask.clone()
+    for ax in range(mask.dim()):
+        pad = torch.zeros_like(mask.narrow(ax, 0, 1))
+        inner &= torch.cat([pad, mask.narrow(ax, 0, mask.shape[ax] - 1)], dim=ax)
+        inner &= torch.cat([mask.narrow(ax, 1, mask.shape[ax] - 1), pad], dim=ax)
+    return mask & ~inner
+
+
+def _directed(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """int64 [len(a)]: squared distance from every coordinate row of ``a`` to the nearest of ``b``."""
+    out = torch.empty(a.shape[0], dtype=torch.int64, device=a.device)
+    step = max(1, _PAIR_CHUNK // max(1, b.shape[0]))
+    for i in range(0, a.shape[0], step):
+        d = a[i:i + step, None, :] - b[None, :, :]
+        out[i:i + step] = (d * d).sum(-1).min(dim=1).values
+    return out
+
+
+@torch.no_grad()
+def case_surface_torch(prob: torch.Tensor, target: torch.Tensor, threshold: float = 0.5, grid=None) -> torch.Tensor:
+    """int64 ``[N][K][4] = {mp, mt, q_lo, q_hi}`` from ``prob`` / ``target`` of shape
+    ``[N, *grid, K]`` (or ``[N, S, K]`` with ``grid`` given): surface coordinates, all-pairs
+    squared distances in int64 and a sort."""
+    n, k = prob.shape[0], prob.shape[-1]
+    grid = _grid_of(prob.shape[1:-1] if grid is None else grid)
+    p32 = prob.reshape((n,) + grid + (k,)).float()
+    t32 = target.reshape((n,) + grid + (k,)).float()
+    pos = p32 >= torch.tensor(threshold, dtype=torch.float32, device=p32.device)
+    fg = t32 >= 0.5
+    out = torch.empty(n, k, NSURF, dtype=torch.int64)
+    for i in range(n):
+        for c in range(k):
+            a = torch.nonzero(_surface(pos[i, ..., c])).long()
+            b = torch.nonzero(_surface(fg[i, ..., c])).long()
+            mp, mt = a.shape[0], b.shape[0]
+            if mp == 0 or mt == 0:
+                out[i, c] = torch.tensor([mp, mt, -1, -1])
+                continue
+            q = torch.sort(torch.cat([_directed(a, b), _directed(b, a)])).values
+            m = mp + mt
+            lo = 95 * (m - 1) // 100
+            hi = min(lo + 1, m - 1)
+            out[i, c] = torch.tensor([mp, mt, int(q[lo]), int(q[hi])])
+    return out
+
+
+def _np_surf(surf) -> np.ndarray:
+    if isinstance(surf, torch.Tensor):
+        surf = surf.detach().cpu().numpy()
+    a = np.asarray(surf, dtype=np.int64)
+    if a.ndim != 3 or a.shape[2] != NSURF:
+        raise ValueError("case surface integers must be [N][K][4], got %s" % (a.shape,))
+    return a
+
+
+def hd95_from_surface(surf, grid) -> np.ndarray:
+    """float64 ``[N][K]`` HD95 in voxels from ``{mp, mt, q_lo, q_hi}`` on ``grid`` = (H, W)
+    or (D, H, W): 0.0 when both surfaces are empty, the grid diagonal when one is."""
+    a = _np_surf(surf)
+    mp, mt = a[:, :, 0], a[:, :, 1]
+    both = (mp > 0) & (mt > 0)
+    r = 95 * (mp + mt - 1)
+    lo = np.sqrt(np.where(both, a[:, :, 2], 0).astype(np.float64))
+    hi = np.sqrt(np.where(both, a[:, :, 3], 0).astype(np.float64))
+    val = lo + (r % 100).astype(np.float64) / 100.0 * (hi - lo)
+    g = tuple(int(v) for v in grid)
+    if len(g) == 2:
+        g = (1,) + g
+    diag = math.sqrt(float(sum(v * v for v in g)))      # sqrt(D^2 + H^2 + W^2), D = 1 in 2D
+    return np.where(both, val, np.where((mp == 0) & (mt == 0), 0.0, diag))
+
+
+def accumulate_hd95(surf, grid, valid=None) -> Dict[str, np.ndarray]:
+    """Additive accumulators of HD95 over the cases of ``surf`` (``valid``: an optional boolean
+    mask over them): the per-class sum and the case count.  Disjoint case sets add."""
+    h = hd95_from_surface(surf, grid)
+    if valid is not None:
+        h = h[np.asarray(valid, dtype=bool)]
+    return {"hd95_sum": h.sum(0), "cases": float(h.shape[0])}
+
+
+def hd95_metrics(acc: Dict[str, np.ndarray]) -> dict:
+    """``{"hd95": [K], "hd95_mean"}``: the mean over cases per class (formed like
+    ``case_dice``) and its mean over classes."""
+    cases = float(acc["cases"])
+    h = [float(v / cases) if cases > 0 else float("nan") for v in acc["hd95_sum"]]
+    return {"hd95": h, "hd95_mean": float(np.mean(h)) if h else float("nan")}
+
+
 def jsonable(o):
     """``o`` with every non-finite float replaced by ``None`` (JSON ``null``): strict JSON
     has no NaN, and an undefined ratio must not read as a number."""

@@ -10,7 +10,8 @@ gradient buffer.
 Both expose ``fwd_bwd(x, y, seed, on_segment)``, ``sums()`` (device tensor
 {I, St, Sp, BCE_sum} of the last forward), ``eval_sums(x, y)`` and the per-(sample,
 class) statistics of ``ops.seg_metrics``: ``last_eval_stats(threshold)`` of the batch the
-last ``eval_sums`` scored (no second forward) and ``eval_stats(x, y, threshold)``.
+last ``eval_sums`` scored (no second forward) and ``eval_stats(x, y, threshold)``; likewise
+``last_eval_surface`` / ``eval_surface`` for the surface-distance integers of HD95.
 """
 
 from typing import Callable, Optional
@@ -107,6 +108,17 @@ class TorchBackend:
         return seg_metrics.case_stats_torch(self.predict(x), y.to(self.device).float(), threshold)
 
     @torch.no_grad()
+    def last_eval_surface(self, threshold: float = 0.5) -> torch.Tensor:
+        """[n][K][4] = {mp, mt, q_lo, q_hi} of the batch the last ``eval_sums`` scored."""
+        t, p = self._last_eval
+        return seg_metrics.case_surface_torch(p, t, threshold)
+
+    @torch.no_grad()
+    def eval_surface(self, x, y, threshold: float = 0.5) -> torch.Tensor:
+        """[n][K][4] = {mp, mt, q_lo, q_hi} per (sample, class) of the n samples given."""
+        return seg_metrics.case_surface_torch(self.predict(x), y.to(self.device).float(), threshold)
+
+    @torch.no_grad()
     def predict(self, x) -> torch.Tensor:
         logits = self._forward_logits(self.flat.params(), x, False, 0, self.cfg.eval_dropout).float()
         return torch.sigmoid(logits)
@@ -128,11 +140,12 @@ class NativeBackend:
             # the reference's precision (test_dist.py:196-202): fp32 storage, fp32 MFMA
             self.engine = NativeUNetF32(spec, flat, per_rank_batch, cfg.img_size, device, loss=cfg.loss,
                                         bce_weight=cfg.bce_weight, bucket_bounds=bounds,
-                                        eval_dropout=cfg.eval_dropout)
+                                        eval_dropout=cfg.eval_dropout, eval_hd95=getattr(cfg, "eval_hd95", False))
         else:
             self.engine = NativeUNet(spec, flat, per_rank_batch, cfg.img_size, device, loss=cfg.loss,
                                      bce_weight=cfg.bce_weight, bucket_bounds=bounds,
-                                     eval_dropout=cfg.eval_dropout, dtype=cfg.dtype)
+                                     eval_dropout=cfg.eval_dropout, dtype=cfg.dtype,
+                                     eval_hd95=getattr(cfg, "eval_hd95", False))
         self.B = per_rank_batch
         if getattr(cfg, "hip_graph", False):
             self.engine.enable_graphs()
@@ -189,17 +202,35 @@ class NativeBackend:
         A short batch is zero-padded to the per-rank batch: evaluation normalises with the
         moving BatchNorm statistics or per sample (GroupNorm), so the padding cannot change
         a real sample's result."""
+        n = self._eval_padded(x, y, "eval_stats")
+        return self.engine.case_stats(threshold)[:n].clone()
+
+    def _eval_padded(self, x, y, what: str) -> int:
+        """Evaluation forward of n <= B samples zero-padded to the per-rank batch; returns n."""
         e = self.engine
         n = x.shape[0]
         if not 1 <= n <= e.B:
-            raise ValueError("native eval_stats takes 1..%d samples (the per-rank batch), got %d" % (e.B, n))
+            raise ValueError("native %s takes 1..%d samples (the per-rank batch), got %d" % (what, e.B, n))
         x, y = x.to(e.device).float(), y.to(e.device).float()
         if n < e.B:
             x = torch.cat([x, x.new_zeros((e.B - n,) + tuple(x.shape[1:]))])
             y = torch.cat([y, y.new_zeros((e.B - n,) + tuple(y.shape[1:]))])
         e.load_batch(x.contiguous(), y.contiguous())
         e.evaluate_batch()
-        return e.case_stats(threshold)[:n].clone()
+        return n
+
+    @torch.no_grad()
+    def last_eval_surface(self, threshold: float = 0.5) -> torch.Tensor:
+        """int32 [B][K][4] = {mp, mt, q_lo, q_hi} of the batch the last ``eval_sums`` scored
+        (surf_dist.h on the probabilities and target the executor still holds)."""
+        return self.engine.case_surface(threshold).clone()
+
+    @torch.no_grad()
+    def eval_surface(self, x, y, threshold: float = 0.5) -> torch.Tensor:
+        """int32 [n][K][4] per (sample, class) of the n <= B samples given; a short batch is
+        zero-padded like ``eval_stats``."""
+        n = self._eval_padded(x, y, "eval_surface")
+        return self.engine.case_surface(threshold)[:n].clone()
 
     @torch.no_grad()
     def predict(self, x) -> torch.Tensor:

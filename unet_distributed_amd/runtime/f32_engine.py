@@ -34,7 +34,8 @@ import torch
 
 from .. import native
 from ..models.spec import UNetSpec
-from .native_engine import gather_aug_args, plan_case_stats, run_case_stats
+from .native_engine import (gather_aug_args, plan_case_stats, plan_case_surface, run_case_stats,
+                            run_case_surface)
 from .params import FlatParams
 from .plan_check import RecordingPlan
 
@@ -50,7 +51,7 @@ class NativeUNetF32:
 
     def __init__(self, spec: UNetSpec, flat: FlatParams, batch: int, img: int, device, loss: str = "dice",
                  bce_weight: float = 1.0, bucket_bounds: Optional[Sequence[int]] = None,
-                 eval_dropout: bool = False, dry_run: bool = False):
+                 eval_dropout: bool = False, dry_run: bool = False, eval_hd95: bool = False):
         self.C = native.require()
         if spec.norm != "none":
             raise NotImplementedError("fp32 native executor: norm=%s (the reference has no normalisation; "
@@ -82,6 +83,9 @@ class NativeUNetF32:
         self._build_forward(self.eval_plan, dropout=eval_dropout)
         self.set_buckets(bucket_bounds)
         plan_case_stats(self, "f32_seg_stats")
+        self.surface_plan = self.case_surface_buf = self.case_surface_scratch = None
+        if eval_hd95:            # (otherwise on the first case_surface call)
+            plan_case_surface(self, "f32_surf_dist")
         self._adam_segs()
 
     # ------------------------------------------------------------------ shapes / buffers
@@ -430,3 +434,8 @@ class NativeUNetF32:
         """[B][1][6] = {I, St, Sp, TP, FP, FN} per sample of the probabilities and the fp32
         target the last forward / evaluate_batch left behind (one launch, seg_stats.h)."""
         return run_case_stats(self, "f32_seg_stats", threshold, stream)
+
+    def case_surface(self, threshold: float = 0.5, stream=None) -> torch.Tensor:
+        """int32 [B][1][4] = {mp, mt, q_lo, q_hi} per sample of the probabilities and the fp32
+        target the last forward / evaluate_batch left behind (surf_dist.h)."""
+        return run_case_surface(self, "f32_surf_dist", threshold, stream)

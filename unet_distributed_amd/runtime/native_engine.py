@@ -217,7 +217,8 @@ class NativeUNet:
     def __init__(self, spec: UNetSpec, flat: FlatParams, batch: int, img: int,
                  device, loss: str = "dice", bce_weight: float = 1.0,
                  bucket_bounds: Optional[Sequence[int]] = None, eval_dropout: bool = False,
-                 dry_run: bool = False, dtype: str = "bf16", opts: Optional[Dict[str, int]] = None):
+                 dry_run: bool = False, dtype: str = "bf16", opts: Optional[Dict[str, int]] = None,
+                 eval_hd95: bool = False):
         self.C = native.require()
         self.opts = engine_options(opts)
         if spec.norm not in ("none", "batch", "group"):
@@ -294,6 +295,9 @@ class NativeUNet:
         self._build_forward(self.eval_plan, dropout=eval_dropout, train=False)
         self.set_buckets(bucket_bounds)
         plan_case_stats(self, "seg_stats")
+        self.surface_plan = self.case_surface_buf = self.case_surface_scratch = None
+        if eval_hd95:            # (otherwise on the first case_surface call: the default trainer does not grow)
+            plan_case_surface(self, "surf_dist")
         if not dry_run:          # dry_run: plan construction only (CPU tests, no GPU launches)
             self.repack()
 
@@ -2164,6 +2168,14 @@ class NativeUNet:
         tensor is the executor's buffer, overwritten by the next call)."""
         return run_case_stats(self, "seg_stats", threshold, stream)
 
+    def case_surface(self, threshold: float = 0.5, stream=None) -> torch.Tensor:
+        """int32 [B][K][4] = {mp, mt, q_lo, q_hi} per (sample, class): the surface sizes of
+        {prob >= threshold} and {target >= 0.5} and the two squared surface distances that
+        bracket the 95th percentile (`ops.seg_metrics.hd95_from_surface`), of the
+        probabilities and target the last forward / evaluate_batch left behind.  The
+        returned tensor is the executor's buffer, overwritten by the next call."""
+        return run_case_surface(self, "surf_dist", threshold, stream)
+
 
 def gather_aug_args(e, x_all, y_all, idx, aug, cin: int, cpad: int, K: int):
     """(ptrs, ints) of an executor's gather_batch_aug / f32_gather_batch_aug launch
@@ -2213,3 +2225,79 @@ def run_case_stats(e, kind: str, threshold: float, stream) -> torch.Tensor:
     ptrs, ints = e._case_stats_args
     e.C.generic(kind, ptrs, ints, [float(threshold)], native.stream_handle(stream), getattr(e, "dt_id", 0))
     return e.case_stats_buf
+
+
+# cap of an executor's surf_dist scratch: the field is 8 bytes per (voxel, class) of a sample
+# group, 384 MiB for K = 3 at b1024 128x128.  256 MiB keeps the 3D b8 128^3 K = 1 batch
+# (128 MiB) and the 2D b1024 K = 1 batch (128 MiB) in one group and splits only the
+# multi-class b1024 batches, into 2 groups of 512 samples that still fill the GPU.
+SURF_SCRATCH_CAP = 256 << 20
+
+
+def surf_dist_group(N: int, sample_bytes: int, scratch_bytes: int) -> int:
+    """Samples per surf_dist launch when the scratch holds `scratch_bytes` and one sample
+    needs `sample_bytes`: the fewest groups that fit, of equal size but for the last."""
+    fit = min(N, scratch_bytes // sample_bytes)
+    if fit < 1:
+        raise ValueError("surf_dist: the scratch (%d bytes) does not hold one sample (%d bytes)"
+                         % (scratch_bytes, sample_bytes))
+    groups = -(-N // fit)
+    return -(-N // groups)
+
+
+def launch_surf_dist(C, kind: str, ptrs, ints, threshold: float, scratch_bytes: int, target_bytes: int,
+                     stream=0, dt_id: int = 0) -> int:
+    """Issue `surf_dist` / `f32_surf_dist` (bindings.cpp) over N samples as immediate ops on
+    groups of consecutive samples that fit the scratch.  ptrs = [prob, target, surf, scratch],
+    ints = [N, D, H, W, K]; `target_bytes`: the target's element size.  prob, target and surf
+    are sample-major, so a group is a pointer offset.  Returns the number of launches."""
+    N, D, H, W, K = ints
+    S = D * H * W
+    g = surf_dist_group(N, C.surf_dist_scratch(1, D, H, W, K), scratch_bytes)
+    prob, tgt, surf, scratch = ptrs
+    n0 = launches = 0
+    while n0 < N:
+        n = min(g, N - n0)
+        C.generic(kind, [prob + n0 * S * K * 4, tgt + n0 * S * K * target_bytes, surf + n0 * K * 16, scratch],
+                  [n, D, H, W, K], [float(threshold)], stream, dt_id)
+        n0 += n
+        launches += 1
+    return launches
+
+
+def plan_case_surface(e, kind: str) -> None:
+    """Buffers and the validation plan of an executor's `case_surface` (kernels/surf_dist.h):
+    the int32 [B][K][4] output and the field scratch, min(one batch, SURF_SCRATCH_CAP).
+
+    Like `case_stats` the op is in neither `plan` nor `eval_plan`: `surface_plan` holds the
+    op of the first sample group alone (threshold 0.5) for the static plan validation."""
+    K = getattr(e, "K", 1)
+    d, h, w = e.sdims(1)
+    e.surface_plan = e.case_surface_buf = e.case_surface_scratch = None
+    try:
+        need = e.C.surf_dist_scratch(e.B, d, h, w, K)
+        group = surf_dist_group(e.B, need // e.B, min(need, SURF_SCRATCH_CAP))
+    except ValueError as err:
+        e._case_surface_err = str(err)
+        return
+    e._case_surface_err = None
+    e._case_surface_group = group
+    e.case_surface_buf = torch.zeros(e.B, K, 4, dtype=torch.int32, device=e.device)
+    e.case_surface_scratch = torch.empty(need // e.B * group // 4, dtype=torch.int32, device=e.device)
+    e._case_surface_args = ([_ptr(e.prob), _ptr(e.target), _ptr(e.case_surface_buf), _ptr(e.case_surface_scratch)],
+                            [e.B, d, h, w, K])
+    e.surface_plan = RecordingPlan(e.C.Plan(getattr(e, "dt_id", 0)))
+    e.surface_plan.add_generic(kind, e._case_surface_args[0], [group, d, h, w, K], [0.5], "case_surface")
+
+
+def run_case_surface(e, kind: str, threshold: float, stream) -> torch.Tensor:
+    if e._dry:
+        raise RuntimeError("executor built with dry_run=True: case_surface is validated, not launched")
+    if e.surface_plan is None and getattr(e, "_case_surface_err", None) is None:
+        plan_case_surface(e, kind)
+    if e._case_surface_err is not None:
+        raise ValueError(e._case_surface_err)
+    ptrs, ints = e._case_surface_args
+    launch_surf_dist(e.C, kind, ptrs, ints, threshold, e.case_surface_scratch.numel() * 4,
+                     e.target.element_size(), native.stream_handle(stream), getattr(e, "dt_id", 0))
+    return e.case_surface_buf

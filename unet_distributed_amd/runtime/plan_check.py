@@ -104,6 +104,10 @@ def _generic_write_spans(kind: str, p: List[int], ints: List[int]) -> List[Tuple
         if len(p) > 3 and p[3] and chunks > 1:
             out.append((p[3], N * chunks * 6 * K * 4))
         return out
+    # surface distances (N, D, H, W, K in ints): N K 4 ints of output and the field scratch
+    if kind in ("surf_dist", "f32_surf_dist") and len(p) > 3 and len(ints) >= 5:
+        N, D, H, W, K = ints[:5]
+        return [(p[2], N * K * 4 * 4), (p[3], surf_dist_scratch(N, D, H, W, K))]
     # augmenting batch gather (B, D, H, W, Cin, Cpad, K in ints): the padded input and the target,
     # 16-bit (gather_batch_aug) or fp32 (f32_gather_batch_aug)
     if kind in ("gather_batch_aug", "f32_gather_batch_aug") and len(p) > 6 and len(ints) >= 7:
@@ -120,6 +124,12 @@ def seg_stats_chunks(N: int, S: int, K: int) -> int:
     chunks = max(1, min(-(-1024 // N), 256, iters))
     per = -(-iters // chunks)
     return -(-iters // per)
+
+
+def surf_dist_scratch(N: int, D: int, H: int, W: int, K: int) -> int:
+    """Scratch bytes of a surf_dist launch over N samples: int32 fields [N][K][2][S]
+    (mirrors csrc/kernels/surf_dist.hip)."""
+    return N * K * 2 * D * H * W * 4
 
 
 def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], List[int]]:
@@ -172,6 +182,8 @@ def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], Li
     if kind == "colsum":
         return _sel(p, [0]), _sel(p, [1])
     if kind in ("seg_stats", "f32_seg_stats"):
+        return _sel(p, [0, 1]), _sel(p, [2, 3])
+    if kind in ("surf_dist", "f32_surf_dist"):
         return _sel(p, [0, 1]), _sel(p, [2, 3])
     if kind in ("gather_batch_aug", "f32_gather_batch_aug"):
         return [q for q in _sel(p, [0, 1, 2, 3, 4]) if q], _sel(p, [5, 6])
@@ -292,7 +304,8 @@ def engine_regions(e) -> Tuple[_Regions, set]:
         if k.startswith("w"):                    # bn/gn_stats workspaces (self-contained)
             inputs.add("stat:" + k)
     for k in ("prob", "target", "sums", "head_partial", "head_ws", "slab", "bias_slab", "red_stage", "arena",
-              "loss_scale_dev", "_no_dy", "case_stats_buf", "case_stats_partial"):
+              "loss_scale_dev", "_no_dy", "case_stats_buf", "case_stats_partial",
+              "case_surface_buf", "case_surface_scratch"):
         R.add(k, getattr(e, k, None))
     inputs |= {"target", "arena", "loss_scale_dev", "_no_dy"}
     for k, t in getattr(e, "state", {}).items():
@@ -367,3 +380,23 @@ def check_stats_plan(e) -> List[str]:
     if e.stats_plan is None:
         return [e._case_stats_err]
     return check_plan(e, e.stats_plan, False, extra_inputs=("prob",))
+
+
+def check_surface_plan(e) -> List[str]:
+    """Errors of executor `e`'s `case_surface` op (`surface_plan`, built on first use or
+    with --eval_hd95): like `case_stats` it reads the probabilities the forward /
+    evaluation plan left behind and the loaded target.  The plan holds the op of the first
+    group of samples; the output must hold every group's rows and the scratch one group."""
+    if getattr(e, "surface_plan", None) is None:
+        return [getattr(e, "_case_surface_err", None) or "case_surface is not planned (plan_case_surface)"]
+    errs = check_plan(e, e.surface_plan, False, extra_inputs=("prob",))
+    K, (d, h, w) = getattr(e, "K", 1), e.sdims(1)
+    if e.case_surface_buf.numel() < e.B * K * 4:
+        errs.append("case_surface: case_surface_buf holds %d ints, B K 4 = %d needed"
+                    % (e.case_surface_buf.numel(), e.B * K * 4))
+    need = surf_dist_scratch(e._case_surface_group, d, h, w, K)
+    have = e.case_surface_scratch.numel() * e.case_surface_scratch.element_size()
+    if have < need:
+        errs.append("case_surface: case_surface_scratch holds %d bytes, a group of %d samples needs %d"
+                    % (have, e._case_surface_group, need))
+    return errs

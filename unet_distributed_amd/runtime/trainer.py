@@ -246,7 +246,8 @@ class Trainer:
         sensitivity and specificity over EVERY test case, `ops.seg_metrics`), `case_dice`
         (their mean over classes) and `cases`.  A full batch costs one more launch on the
         forward its `eval_sums` ran; the `n % B` tail is one padded `eval_stats` call on
-        rank `nbatches % world`."""
+        rank `nbatches % world`.  With `--eval_hd95` the same cases also give `per_class["hd95"]`
+        and `hd95` (voxels; `last_eval_surface` per full batch, `eval_surface` for the tail)."""
         n = len(self.x_test)
         B = self.per_rank
         nbatches = n // B
@@ -260,6 +261,12 @@ class Trainer:
             a = seg_metrics.accumulate(stats, S)
             cls[K:] += np.concatenate([a["case_dice_sum"], a["tp"], a["fp"], a["fn"], a["tn"], [a["cases"]]])
 
+        hd = np.zeros(K, dtype=np.float64)      # --eval_hd95: per-class sum over the cases of HD95 (voxels)
+        want_hd = self.cfg.eval_hd95
+
+        def surface(surf, y):
+            hd[:] += seg_metrics.accumulate_hd95(surf, tuple(y.shape[1:-1]))["hd95_sum"]
+
         def load(lo, hi):
             return (torch.from_numpy(np.ascontiguousarray(self.x_test[lo:hi])).to(self.device),
                     torch.from_numpy(np.ascontiguousarray(self.y_test[lo:hi])).to(self.device))
@@ -272,22 +279,31 @@ class Trainer:
             stats = self.backend.last_eval_stats(thr)
             cls[:K] += seg_metrics.soft_dice(stats)
             hard(stats, y[0].numel() // K)
+            if want_hd:
+                surface(self.backend.last_eval_surface(thr), y)
         if n % B and self.rank == nbatches % self.world:
             x, y = load(nbatches * B, n)
             hard(self.backend.eval_stats(x, y, thr), y[0].numel() // K)
+            if want_hd:
+                surface(self.backend.eval_surface(x, y, thr), y)
         D.allreduce_sum_(acc)
-        cls_t = torch.from_numpy(cls).to(self.device)
+        cls_t = torch.from_numpy(np.concatenate([cls, hd]) if want_hd else cls).to(self.device)
         D.allreduce_sum_(cls_t)                 # (every rank, whether or not it owns the tail)
         cls = cls_t.cpu().numpy()
         cnt = max(acc[4].item(), 1.0)
         hm = seg_metrics.hard_metrics({"case_dice_sum": cls[K:2 * K], "tp": cls[2 * K:3 * K], "fp": cls[3 * K:4 * K],
                                        "fn": cls[4 * K:5 * K], "tn": cls[5 * K:6 * K], "cases": cls[6 * K]})
-        return {"loss": acc[0].item() / cnt, "dice": acc[1].item() / cnt,
-                "sensitivity": acc[2].item() / cnt, "specificity": acc[3].item() / cnt,
-                "batches": int(acc[4].item()),
-                "per_class": {"dice": [float(v) / cnt for v in cls[:K]], "case_dice": hm["case_dice"],
-                              "sensitivity": hm["sensitivity"], "specificity": hm["specificity"]},
-                "case_dice": hm["case_dice_mean"], "cases": hm["cases"]}
+        m = {"loss": acc[0].item() / cnt, "dice": acc[1].item() / cnt,
+             "sensitivity": acc[2].item() / cnt, "specificity": acc[3].item() / cnt,
+             "batches": int(acc[4].item()),
+             "per_class": {"dice": [float(v) / cnt for v in cls[:K]], "case_dice": hm["case_dice"],
+                           "sensitivity": hm["sensitivity"], "specificity": hm["specificity"]},
+             "case_dice": hm["case_dice_mean"], "cases": hm["cases"]}
+        if want_hd:
+            hm95 = seg_metrics.hd95_metrics({"hd95_sum": cls[6 * K + 1:7 * K + 1], "cases": cls[6 * K]})
+            m["per_class"]["hd95"] = hm95["hd95"]
+            m["hd95"] = hm95["hd95_mean"]
+        return m
 
     # ------------------------------------------------------------------ step
     def _poison_due(self, step: int) -> bool:

@@ -43,6 +43,8 @@ def main(argv=None) -> float:
     p.add_argument("--all_batches", action="store_true")
     p.add_argument("--per_class", action="store_true",
                    help="also print per-class case Dice, sensitivity and specificity (thresholded at 0.5)")
+    p.add_argument("--hd95", action="store_true",
+                   help="also print the per-class 95th-percentile Hausdorff distance in voxels (thresholded at 0.5)")
     p.add_argument("--synthetic", type=int, default=0, metavar="N",
                    help="use N synthetic test slices instead of the .npy files")
     a = p.parse_args(argv)
@@ -82,6 +84,15 @@ def main(argv=None) -> float:
                 k, seg_metrics.fmt(m["case_dice"][k]), seg_metrics.fmt(m["sensitivity"][k]),
                 seg_metrics.fmt(m["specificity"][k])))
         print("Case Dice = {} ({} cases)".format(seg_metrics.fmt(m["case_dice_mean"]), m["cases"]))
+    if a.hd95 and nb:
+        from .ops import seg_metrics
+        surf = [model.surface(np.asarray(x[s:s + a.batch_size], dtype=np.float32),
+                              np.asarray(y[s:s + a.batch_size], dtype=np.float32))
+                for s in batch_starts(len(x), a.batch_size, a.all_batches)]
+        m = seg_metrics.hd95_metrics(seg_metrics.accumulate_hd95(np.concatenate(surf), tuple(y.shape[1:-1])))
+        for k in range(len(m["hd95"])):
+            print("class {}: HD95 = {}".format(k, seg_metrics.fmt(m["hd95"][k])))
+        print("HD95 = {} ({} cases)".format(seg_metrics.fmt(m["hd95_mean"]), sum(len(s) for s in surf)))
     print("({} batches, {} backend, {:.1f} images/sec)".format(nb, model.name, nb * a.batch_size / max(dt, 1e-9)))
     return avg
 

@@ -78,6 +78,10 @@ class MetricLogger:
                     k, fmt(pc["dice"][k]), fmt(pc["case_dice"][k]), fmt(pc["sensitivity"][k]),
                     fmt(pc["specificity"][k])))
             print("Case Dice = {} ({} cases)".format(fmt(m["case_dice"]), m["cases"]), flush=True)
+            if "hd95" in pc:                    # --eval_hd95: in voxels
+                for k in range(len(pc["hd95"])):
+                    print("class {}: HD95 = {}".format(k, fmt(pc["hd95"][k])))
+                print("HD95 = {} ({} cases)".format(fmt(m["hd95"]), m["cases"]), flush=True)
         self._emit(dict(kind="test_final" if final else "test", step=step, **m))
         if self.events:
             self.events.scalars(step, {"loss_test": m["loss"], "dice_test": m["dice"],
@@ -88,6 +92,10 @@ class MetricLogger:
                 for k in range(len(pc["dice"])):
                     tags["dice_test/class_%d" % k] = pc["dice"][k]
                     tags["case_dice_test/class_%d" % k] = pc["case_dice"][k]
+                if "hd95" in pc:
+                    tags["hd95_test"] = m["hd95"]
+                    for k in range(len(pc["hd95"])):
+                        tags["hd95_test/class_%d" % k] = pc["hd95"][k]
                 self.events.scalars(step, tags)
             self.events.flush()
 
