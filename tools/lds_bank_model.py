@@ -240,7 +240,28 @@ def check_gather_aug_target(pitch=33):
     return w, r
 
 
+# ---------------------------------------------------------------- tta_acc tile transpose
+# tta.h tta_acc_kernel: 32 x 32 pixel tile of K fp32 per pixel, rows of 33 K floats.  Lane
+# tid's float f = tid + 256 i (i < 4 K) is pixel q = f // K, class k = f % K: written at
+# [q >> 5][(q & 31) K + k] (a row of the source) and read back from [q & 31][(q >> 5) K + k]
+# (a row of the output); 4-byte accesses, serviced in 32-lane halves over 32 banks.
+def check_tta_tile(K, pitch=None):
+    """(write ways, transposed-read ways) of the probability tile."""
+    pitch = 33 * K if pitch is None else pitch
+    w = r = 1
+    for wave in range(4):
+        for i in range(4 * K):
+            f = [64 * wave + l + 256 * i for l in range(64)]
+            q = [v // K for v in f]
+            k = [v % K for v in f]
+            w = max(w, ways([4 * ((q[l] >> 5) * pitch + (q[l] & 31) * K + k[l]) for l in range(64)], 4, HALVES, 32))
+            r = max(r, ways([4 * ((q[l] & 31) * pitch + (q[l] >> 5) * K + k[l]) for l in range(64)], 4, HALVES, 32))
+    return w, r
+
+
 if __name__ == "__main__":
+    print("tta_acc tile (write, transposed read) ways K=1..4, unpadded:",
+          [check_tta_tile(K) for K in (1, 2, 3, 4)], [check_tta_tile(K, 32 * K) for K in (1, 2, 3, 4)])
     print("gather_aug tile (write, transposed read) ways nw=2/4/8, unpadded nw=2/4:",
           [check_gather_aug(n) for n in (2, 4, 8)], [check_gather_aug(n, 0) for n in (2, 4)],
           "target plane:", check_gather_aug_target(), check_gather_aug_target(32))

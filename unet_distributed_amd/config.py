@@ -105,6 +105,7 @@ class Config:
     eval_hd95: bool = False          # evaluation also reports the per-case 95th-percentile Hausdorff distance
     augment: str = ""                # training batches only: comma-separated subset of flip, rot90, intensity
     augment_intensity: float = 0.1   # intensity: scale in [1-a, 1+a], shift in [-a, a] per (sample, channel)
+    eval_tta: str = ""               # evaluation only: mean prediction over flip and / or rot90 (comma-separated)
 
     @property
     def method_up(self):
@@ -141,6 +142,21 @@ def parse_augment(s: str) -> tuple:
             raise SystemExit("--augment: unknown transform %r (choose from %s)" % (t, ", ".join(AUGMENT_NAMES)))
         if t in names[:i]:
             raise SystemExit("--augment: %r is listed twice" % t)
+    return tuple(names)
+
+
+TTA_NAMES = ("flip", "rot90")
+
+
+def parse_tta(s: str) -> tuple:
+    """The --eval_tta string as a tuple of transform names (the geometric ones of --augment);
+    an unknown or repeated name is a SystemExit that names it."""
+    names = [t.strip() for t in str(s).split(",")] if str(s).strip() else []
+    for i, t in enumerate(names):
+        if t not in TTA_NAMES:
+            raise SystemExit("--eval_tta: unknown transform %r (choose from %s)" % (t, ", ".join(TTA_NAMES)))
+        if t in names[:i]:
+            raise SystemExit("--eval_tta: %r is listed twice" % t)
     return tuple(names)
 
 
@@ -190,6 +206,7 @@ def validate(cfg: Config) -> None:
     if not 0.0 < cfg.eval_threshold < 1.0:
         raise SystemExit("--eval_threshold must lie strictly inside (0, 1)")
     parse_augment(cfg.augment)
+    parse_tta(cfg.eval_tta)
     if not 0.0 <= cfg.augment_intensity < 1.0:
         raise SystemExit("--augment_intensity must be in [0, 1)")
     if cfg.mode == 5 and cfg.out_channels > 3:

@@ -297,6 +297,7 @@ F32Wgrad f32_wgrad_params(const py::dict& d) {
   X(head_dy_launch) \
   X(seg_stats_launch) \
   X(surf_dist_launch) \
+  X(tta_finish_launch) \
   X(partial_reduce_launch) \
   X(head_finish_launch) \
   X(norm_head_launch) \
@@ -691,8 +692,42 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
       };
     return [=](hipStream_t s) { return A->surf_dist_launch(prob, t, n, d, h, w, K, thr, field, surf, s); };
   }
+  if (kind == "tta_acc") {
+    // ptrs: prob (fp32 [N][D][H][W][K]), acc (the same shape)
+    // ints: N, D, H, W, K, code (0..15; bits outside the dims are ignored), mode (0: acc = ..., 1: acc += ...)
+    need(2, 7, 0);
+    check_msg(tta_acc_check(I[0], I[1], I[2], I[3], I[4], I[5], I[6]));
+    const float* prob = (const float*)vp(0);
+    float* acc = (float*)vp(1);
+    if (!prob || !acc) throw std::invalid_argument("tta_acc: prob / acc required");
+    const int n = (int)I[0], d = (int)I[1], h = (int)I[2], w = (int)I[3], K = (int)I[4], code = (int)I[5],
+              mode = (int)I[6];
+    return [=](hipStream_t s) { return unet::tta_acc_launch(prob, acc, n, d, h, w, K, code, mode, s); };
+  }
+  if (kind == "tta_finish" || kind == "f32_tta_finish") {
+    // ptrs: prob (fp32, in place), acc (fp32), target (tta_finish: the 16-bit type, f32_tta_finish: fp32),
+    //       partial (tta_finish_blocks(total) * 4 floats), sums (fp32 [4] = {I, St, Sp, BCE})
+    // ints: total elements (N S K, a multiple of 4)   floats: 1 / M
+    need(5, 1, 1);
+    check_msg(tta_finish_check(I[0]));
+    float* prob = (float*)vp(0);
+    const float* acc = (const float*)vp(1);
+    const void* t = vp(2);
+    float *part = (float*)vp(3), *sums = (float*)vp(4);
+    if (!prob || !acc || !t || !part || !sums)
+      throw std::invalid_argument("tta_finish: prob / acc / target / partial / sums required");
+    if ((P[0] & 15) || (P[1] & 15) || (P[2] & (kind == "f32_tta_finish" ? 15 : 7)))
+      throw std::invalid_argument("tta_finish: prob / acc / target must be aligned to 4 elements");
+    const long long total = I[0];
+    const float inv_m = (float)F[0];
+    if (kind == "f32_tta_finish")
+      return [=](hipStream_t s) {
+        return unet::f32_tta_finish_launch(prob, acc, (const float*)t, total, inv_m, part, sums, s);
+      };
+    return [=](hipStream_t s) { return A->tta_finish_launch(prob, acc, t, total, inv_m, part, sums, s); };
+  }
   if (kind == "norm_moments") {
-    // ptrs: A, B, partial, S   ints: N, P, C    (S[n][2][C] = per-sample sums of A and A*B)
+    // ptrs: A, B, partial, S  ints: N, P, C    (S[n][2][C] = per-sample sums of A and A*B)
     need(4, 3, 0);
     void *a = vp(0), *b = vp(1);
     float *part = (float*)vp(2), *S = (float*)vp(3);
@@ -1058,6 +1093,11 @@ PYBIND11_MODULE(_C, m) {
     check_msg(seg_stats_check(N, S, K));
     return seg_stats_chunks((int)N, (int)S, (int)K);
   }, py::arg("N"), py::arg("S"), py::arg("K"));
+  // blocks of a tta_finish launch over `total` elements: its partial buffer is blocks * 4 floats
+  m.def("tta_finish_blocks", [](long long total) {
+    check_msg(tta_finish_check(total));
+    return tta_finish_blocks(total);
+  }, py::arg("total"));
   // bytes of the scratch of a surf_dist launch over N samples (int32 fields [N][K][2][S])
   m.def("surf_dist_scratch", [](long long N, long long D, long long H, long long W, long long K) {
     check_msg(surf_dist_check(N, D, H, W, K));

@@ -113,6 +113,19 @@ long long surf_dist_scratch(long long N, long long D, long long H, long long W, 
 hipError_t surf_dist_launch(const float* prob, const void* t, int N, int D, int H, int W, int K, float thr, int* field,
                             int* surf, hipStream_t s);
 
+// test-time augmentation (tta.h): acc (= | +=) prob under one transform code (fp32 [N][D][H][W][K],
+// H == W; mode 0 writes, 1 adds), then prob = (acc + prob) * inv_m in place with the loss sums
+// {I, St, Sp, BCE} of that mean against t (the build's 16-bit type);
+// partial: tta_finish_blocks(total) * 4 floats
+const char* tta_acc_check(long long N, long long D, long long H, long long W, long long K, long long code,
+                          long long mode);
+const char* tta_finish_check(long long total);
+int tta_finish_blocks(long long total);
+hipError_t tta_acc_launch(const float* prob, float* acc, int N, int D, int H, int W, int K, int code, int mode,
+                          hipStream_t s);
+hipError_t tta_finish_launch(float* prob, const float* acc, const void* t, long long total, float inv_m,
+                             float* partial, float* sums, hipStream_t s);
+
 int norm_blocks_per_sample(int N, int P);
 int sample_slices(int N);  // partial workspace of the finalize launchers: sample_slices(N) * 2 * C floats
 const char* norm_check(int C, int G);
@@ -190,4 +203,7 @@ hipError_t f32_gather_batch_aug_launch(const float* x_all, const float* y_all, c
 // surf_dist with an fp32 target (f32_surf_dist.hip)
 hipError_t f32_surf_dist_launch(const float* prob, const float* t, int N, int D, int H, int W, int K, float thr,
                                 int* field, int* surf, hipStream_t s);
+// tta_finish with an fp32 target (f32_tta.hip)
+hipError_t f32_tta_finish_launch(float* prob, const float* acc, const float* t, long long total, float inv_m,
+                                 float* partial, float* sums, hipStream_t s);
 hipError_t f32_transpose_launch(const float* src, int T, int A, int B, int flip, float* dst, hipStream_t s);

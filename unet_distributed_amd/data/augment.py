@@ -22,7 +22,7 @@ from typing import Callable, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..config import parse_augment
+from ..config import parse_augment, parse_tta
 
 FW, FH, T, FD = 1, 2, 4, 8
 # np.rot90(m, k) of the (H, W) plane for k = 0..3 as codes
@@ -129,6 +129,42 @@ def apply_torch(x, y, code, affine=None):
         af = af.view((n,) + (1,) * (x.dim() - 2) + (af.shape[1], 2))
         xo = (xo.double() * af[..., 0] + af[..., 1]).to(x.dtype)
     return xo, yo
+
+
+def tta_codes(spec, dims: int) -> Tuple[int, ...]:
+    """The transform codes of test-time augmentation `spec` (the --eval_tta string or its
+    parsed names): `flip` every subset of the flips of the sample's axes, `rot90` the four
+    quarter turns, both every code; ascending with the identity LAST (the executors' identity
+    pass leaves the stored target behind).  M = len is a power of two (1 / M is exact); () is off."""
+    names = parse_tta(spec) if isinstance(spec, str) else tuple(spec)
+    flip, rot = "flip" in names, "rot90" in names
+    if flip and rot:
+        codes = range(16 if dims == 3 else 8)
+    elif flip:
+        bits = FW | FH | (FD if dims == 3 else 0)
+        codes = [c for c in range(16) if not c & ~bits]
+    elif rot:
+        codes = ROT90_CODES
+    else:
+        return ()
+    return tuple(sorted(c for c in codes if c)) + (0,)
+
+
+def tta_mean_torch(predict_fn, x, codes):
+    """Mean over `codes` (tta_codes: the identity last) of predict_fn's probabilities of the
+    transformed batch x [n, (D,) H, W, C], each brought back by its inverse transform.  The
+    arithmetic is the HIP path's (kernels/tta.h), in its order: acc = unaug(p_c0);
+    acc = acc + unaug(p_ci) for each later code; p = (acc + p_identity) * (1 / M) in fp32."""
+    codes = tuple(int(c) for c in codes)
+    if len(codes) < 2 or codes[-1] != 0 or 0 in codes[:-1] or len(codes) & (len(codes) - 1):
+        raise ValueError("tta_mean_torch: a power of two >= 2 of codes with the identity last, got %r" % (codes,))
+    n = x.shape[0]
+    acc = None
+    for c in codes[:-1]:
+        p = predict_fn(apply_torch(x, x, [c] * n)[0]).float()
+        u = apply_torch(p, p, [inverse_code(c)] * n)[0]
+        acc = u if acc is None else acc + u
+    return (acc + predict_fn(x).float()) * (1.0 / len(codes))
 
 
 def make_aug(cfg, step: int) -> Optional[Callable[[Sequence[int]], Tuple[np.ndarray, Optional[np.ndarray]]]]:

@@ -33,7 +33,8 @@ from .utils.checkpoint import tensors_to_flat
 class _Cfg:
     """Minimal config for the backends (inference needs no optimiser flags)."""
 
-    def __init__(self, img_size, dtype, eval_dropout=False):
+    def __init__(self, img_size, dtype, eval_dropout=False, eval_tta=""):
+        self.eval_tta = eval_tta
         self.img_size = img_size
         self.dtype = dtype
         self.loss = "dice"
@@ -44,11 +45,15 @@ class _Cfg:
 
 class Predictor:
     def __init__(self, spec: UNetSpec, flat: FlatParams, img_size: int, device, batch: int,
-                 dtype: str = "bf16", backend: str = "auto", state=None):
+                 dtype: str = "bf16", backend: str = "auto", state=None, tta: str = ""):
+        """`tta`: test-time augmentation, a comma list of flip and rot90 (the --eval_tta
+        spelling): `predict`, `stats` and `surface` then score the mean over the transforms."""
+        from .config import parse_tta
         from .runtime.backends import NativeBackend, TorchBackend, resolve_backend
         self.spec, self.flat, self.batch, self.img_size = spec, flat, batch, img_size
         self.device = torch.device(device)
-        cfg = _Cfg(img_size, dtype if self.device.type == "cuda" else "fp32")
+        parse_tta(tta)
+        cfg = _Cfg(img_size, dtype if self.device.type == "cuda" else "fp32", eval_tta=tta)
         if resolve_backend(backend, spec, cfg, self.device) == "native":
             from . import native
             native.require()
@@ -135,7 +140,7 @@ def _spec_from_json(path: str):
 
 
 def load_saved_model(export_dir: str, device=None, batch: int = 128, dtype: str = "bf16",
-                     backend: str = "auto") -> Predictor:
+                     backend: str = "auto", tta: str = "") -> Predictor:
     pb = os.path.join(export_dir, "saved_model.pb")
     if os.path.exists(pb):
         spec, img_size = _spec_from_pb(pb)
@@ -147,4 +152,5 @@ def load_saved_model(export_dir: str, device=None, batch: int = 128, dtype: str 
     tensors = tf_bundle.read_bundle(os.path.join(export_dir, "variables", "variables"))
     tensors_to_flat(flat, tensors, strict=True)
     state = {k: v for k, v in tensors.items() if k.endswith("moving_mean") or k.endswith("moving_variance")}
-    return Predictor(spec, flat, int(img_size), device, batch, dtype=dtype, backend=backend, state=state)
+    return Predictor(spec, flat, int(img_size), device, batch, dtype=dtype, backend=backend, state=state,
+                     tta=tta)

@@ -12,12 +12,16 @@ Both expose ``fwd_bwd(x, y, seed, on_segment)``, ``sums()`` (device tensor
 class) statistics of ``ops.seg_metrics``: ``last_eval_stats(threshold)`` of the batch the
 last ``eval_sums`` scored (no second forward) and ``eval_stats(x, y, threshold)``; likewise
 ``last_eval_surface`` / ``eval_surface`` for the surface-distance integers of HD95.
+With ``--eval_tta`` every one of these evaluation forwards (``predict`` too) is the mean of
+the probabilities over the flipped / rotated inputs (``data.augment.tta_mean_torch`` on
+ATen, the executors' ``evaluate_tta`` on the HIP path); training steps are untouched.
 """
 
 from typing import Callable, Optional
 
 import torch
 
+from ..data.augment import tta_codes, tta_mean_torch
 from ..models import reference
 from ..ops import losses, seg_metrics
 from .params import FlatParams
@@ -44,6 +48,8 @@ class TorchBackend:
         # allreduce buckets: on_segment(k) is called once per bucket after the backward
         # (the GradSync of the trainer is planned with the same bounds)
         self.bounds = list(bounds) if bounds else [flat.numel]
+        # --eval_tta: the transform codes every evaluation forward is averaged over (() = off)
+        self.tta = tta_codes(getattr(cfg, "eval_tta", ""), spec.dims)
 
     def set_buckets(self, bounds):
         self.bounds = list(bounds)
@@ -88,8 +94,14 @@ class TorchBackend:
 
     @torch.no_grad()
     def eval_sums(self, x, y) -> torch.Tensor:
-        logits = self._forward_logits(self.flat.params(), x, False, 0, self.cfg.eval_dropout).float()
         t = y.to(self.device).float()
+        if self.tta:
+            # the mean probability has no logits: BCE from the probabilities (log clamped at -100)
+            p = self.predict(x)
+            self._last_eval = (t, p)
+            i, st, sp = losses.dice_sums(t, p)
+            return torch.stack([i, st, sp, torch.nn.functional.binary_cross_entropy(p, t, reduction="sum")])
+        logits = self._forward_logits(self.flat.params(), x, False, 0, self.cfg.eval_dropout).float()
         p = torch.sigmoid(logits)
         self._last_eval = (t, p)
         i, st, sp = losses.dice_sums(t, p)
@@ -118,10 +130,16 @@ class TorchBackend:
         """[n][K][4] = {mp, mt, q_lo, q_hi} per (sample, class) of the n samples given."""
         return seg_metrics.case_surface_torch(self.predict(x), y.to(self.device).float(), threshold)
 
-    @torch.no_grad()
-    def predict(self, x) -> torch.Tensor:
+    def _predict1(self, x) -> torch.Tensor:
         logits = self._forward_logits(self.flat.params(), x, False, 0, self.cfg.eval_dropout).float()
         return torch.sigmoid(logits)
+
+    @torch.no_grad()
+    def predict(self, x) -> torch.Tensor:
+        """Probabilities of x; with --eval_tta their mean over the transforms (`tta_mean_torch`)."""
+        if self.tta:
+            return tta_mean_torch(self._predict1, x.to(self.device), self.tta)
+        return self._predict1(x)
 
     def after_optimizer(self):
         pass
@@ -136,16 +154,19 @@ class NativeBackend:
         self.cfg = cfg
         self.flat = flat
         self.spec = spec
+        # --eval_tta: the transform codes every evaluation forward is averaged over (() = off)
+        self.tta = tta_codes(getattr(cfg, "eval_tta", ""), spec.dims)
         if cfg.dtype == "fp32":
             # the reference's precision (test_dist.py:196-202): fp32 storage, fp32 MFMA
             self.engine = NativeUNetF32(spec, flat, per_rank_batch, cfg.img_size, device, loss=cfg.loss,
                                         bce_weight=cfg.bce_weight, bucket_bounds=bounds,
-                                        eval_dropout=cfg.eval_dropout, eval_hd95=getattr(cfg, "eval_hd95", False))
+                                        eval_dropout=cfg.eval_dropout, eval_hd95=getattr(cfg, "eval_hd95", False),
+                                        eval_tta=bool(self.tta))
         else:
             self.engine = NativeUNet(spec, flat, per_rank_batch, cfg.img_size, device, loss=cfg.loss,
                                      bce_weight=cfg.bce_weight, bucket_bounds=bounds,
                                      eval_dropout=cfg.eval_dropout, dtype=cfg.dtype,
-                                     eval_hd95=getattr(cfg, "eval_hd95", False))
+                                     eval_hd95=getattr(cfg, "eval_hd95", False), eval_tta=bool(self.tta))
         self.B = per_rank_batch
         if getattr(cfg, "hip_graph", False):
             self.engine.enable_graphs()
@@ -186,9 +207,18 @@ class NativeBackend:
         e = self.engine
         if x.shape[0] != e.B:
             raise ValueError("native eval batch must equal the per-rank batch")
-        e.load_batch(x, y)
-        e.evaluate_batch()
+        self._evaluate(x, y)
         return e.sums.clone()
+
+    def _evaluate(self, x, y) -> None:
+        """One evaluation of the full batch (x, y): the plain forward, or with --eval_tta the
+        executor's `evaluate_tta` (the mean over the transforms; `sums` are then the mean's)."""
+        e = self.engine
+        if self.tta:
+            e.evaluate_tta(x, y, self.tta)
+        else:
+            e.load_batch(x, y)
+            e.evaluate_batch()
 
     @torch.no_grad()
     def last_eval_stats(self, threshold: float = 0.5) -> torch.Tensor:
@@ -215,8 +245,7 @@ class NativeBackend:
         if n < e.B:
             x = torch.cat([x, x.new_zeros((e.B - n,) + tuple(x.shape[1:]))])
             y = torch.cat([y, y.new_zeros((e.B - n,) + tuple(y.shape[1:]))])
-        e.load_batch(x.contiguous(), y.contiguous())
-        e.evaluate_batch()
+        self._evaluate(x.contiguous(), y.contiguous())
         return n
 
     @torch.no_grad()
@@ -235,8 +264,7 @@ class NativeBackend:
     @torch.no_grad()
     def predict(self, x) -> torch.Tensor:
         e = self.engine
-        e.load_batch(x, torch.zeros(x.shape[:-1] + (self.spec.n_cl_out,), device=x.device))
-        e.evaluate_batch()
+        self._evaluate(x, torch.zeros(x.shape[:-1] + (self.spec.n_cl_out,), device=x.device))
         return e.probs().clone()
 
     def adam_step(self, lr, b1p, b2p, grad_scale=1.0):

@@ -34,8 +34,8 @@ import torch
 
 from .. import native
 from ..models.spec import UNetSpec
-from .native_engine import (gather_aug_args, plan_case_stats, plan_case_surface, run_case_stats,
-                            run_case_surface)
+from .native_engine import (gather_aug_args, plan_case_stats, plan_case_surface, plan_tta, run_case_stats,
+                            run_case_surface, run_evaluate_tta)
 from .params import FlatParams
 from .plan_check import RecordingPlan
 
@@ -51,7 +51,8 @@ class NativeUNetF32:
 
     def __init__(self, spec: UNetSpec, flat: FlatParams, batch: int, img: int, device, loss: str = "dice",
                  bce_weight: float = 1.0, bucket_bounds: Optional[Sequence[int]] = None,
-                 eval_dropout: bool = False, dry_run: bool = False, eval_hd95: bool = False):
+                 eval_dropout: bool = False, dry_run: bool = False, eval_hd95: bool = False,
+                 eval_tta: bool = False):
         self.C = native.require()
         if spec.norm != "none":
             raise NotImplementedError("fp32 native executor: norm=%s (the reference has no normalisation; "
@@ -86,6 +87,9 @@ class NativeUNetF32:
         self.surface_plan = self.case_surface_buf = self.case_surface_scratch = None
         if eval_hd95:            # (otherwise on the first case_surface call)
             plan_case_surface(self, "f32_surf_dist")
+        self.tta_plan = self.tta_acc_buf = self.tta_partial = None
+        if eval_tta:             # (otherwise on the first evaluate_tta call)
+            plan_tta(self, "f32_tta_finish")
         self._adam_segs()
 
     # ------------------------------------------------------------------ shapes / buffers
@@ -439,3 +443,9 @@ class NativeUNetF32:
         """int32 [B][1][4] = {mp, mt, q_lo, q_hi} per sample of the probabilities and the fp32
         target the last forward / evaluate_batch left behind (surf_dist.h)."""
         return run_case_surface(self, "f32_surf_dist", threshold, stream)
+
+    def evaluate_tta(self, x: torch.Tensor, y: torch.Tensor, codes, stream=None):
+        """Test-time augmentation of the batch (x, y) over the transform codes `codes`
+        (`data.augment.tta_codes`): `prob` then holds the mean, `target` the stored target and
+        `sums` the sums of that mean (tta.h, `native_engine.run_evaluate_tta`)."""
+        return run_evaluate_tta(self, x, y, codes, stream)

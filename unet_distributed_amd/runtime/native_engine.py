@@ -218,7 +218,7 @@ class NativeUNet:
                  device, loss: str = "dice", bce_weight: float = 1.0,
                  bucket_bounds: Optional[Sequence[int]] = None, eval_dropout: bool = False,
                  dry_run: bool = False, dtype: str = "bf16", opts: Optional[Dict[str, int]] = None,
-                 eval_hd95: bool = False):
+                 eval_hd95: bool = False, eval_tta: bool = False):
         self.C = native.require()
         self.opts = engine_options(opts)
         if spec.norm not in ("none", "batch", "group"):
@@ -298,6 +298,9 @@ class NativeUNet:
         self.surface_plan = self.case_surface_buf = self.case_surface_scratch = None
         if eval_hd95:            # (otherwise on the first case_surface call: the default trainer does not grow)
             plan_case_surface(self, "surf_dist")
+        self.tta_plan = self.tta_acc_buf = self.tta_partial = None
+        if eval_tta:             # (otherwise on the first evaluate_tta call)
+            plan_tta(self, "tta_finish")
         if not dry_run:          # dry_run: plan construction only (CPU tests, no GPU launches)
             self.repack()
 
@@ -2176,6 +2179,12 @@ class NativeUNet:
         returned tensor is the executor's buffer, overwritten by the next call."""
         return run_case_surface(self, "surf_dist", threshold, stream)
 
+    def evaluate_tta(self, x: torch.Tensor, y: torch.Tensor, codes, stream=None):
+        """Test-time augmentation of the batch (x, y) over the transform codes `codes`
+        (`data.augment.tta_codes`): afterwards `prob` holds the mean of the un-augmented
+        probabilities, `target` the stored target and `sums` the sums of that mean."""
+        return run_evaluate_tta(self, x, y, codes, stream)
+
 
 def gather_aug_args(e, x_all, y_all, idx, aug, cin: int, cpad: int, K: int):
     """(ptrs, ints) of an executor's gather_batch_aug / f32_gather_batch_aug launch
@@ -2301,3 +2310,66 @@ def run_case_surface(e, kind: str, threshold: float, stream) -> torch.Tensor:
     launch_surf_dist(e.C, kind, ptrs, ints, threshold, e.case_surface_scratch.numel() * 4,
                      e.target.element_size(), native.stream_handle(stream), getattr(e, "dt_id", 0))
     return e.case_surface_buf
+
+
+def plan_tta(e, finish_kind: str) -> None:
+    """Buffers and the validation plan of an executor's `evaluate_tta` (kernels/tta.h): the
+    accumulator, the size of `prob`, and the finish's block partials.  Like `case_stats` the
+    ops are in neither `plan` nor `eval_plan`: `tta_plan` holds one tta_acc that writes, one
+    that adds and the finish (M = 4) for the static plan validation; the [M][B] code rows of
+    a code set are made on its first use."""
+    K = getattr(e, "K", 1)
+    d, h, w = e.sdims(1)
+    total = e.prob.numel()
+    e.tta_acc_buf = torch.empty_like(e.prob)
+    e.tta_partial = torch.zeros(e.C.tta_finish_blocks(total) * 4, dtype=torch.float32, device=e.device)
+    e._tta_rows = {}
+    e._tta_finish_kind = finish_kind
+    e._tta_acc_args = ([_ptr(e.prob), _ptr(e.tta_acc_buf)], [e.B, d, h, w, K])
+    e._tta_finish_args = ([_ptr(e.prob), _ptr(e.tta_acc_buf), _ptr(e.target), _ptr(e.tta_partial), _ptr(e.sums)],
+                          [total])
+    e.tta_plan = RecordingPlan(e.C.Plan(getattr(e, "dt_id", 0)))
+    ptrs, ints = e._tta_acc_args
+    # (code 1 = FW: the strip path; code 5 = T | FW: the tile path)
+    e.tta_plan.add_generic("tta_acc", ptrs, ints + [1, 0], [], "tta_acc:write")
+    e.tta_plan.add_generic("tta_acc", ptrs, ints + [5, 1], [], "tta_acc:add")
+    e.tta_plan.add_generic(finish_kind, e._tta_finish_args[0], e._tta_finish_args[1], [0.25], "tta_finish")
+
+
+def run_evaluate_tta(e, x: torch.Tensor, y: torch.Tensor, codes, stream=None) -> None:
+    """Test-time augmentation of one batch x [B, (D,) H, W, Cin], y [B, (D,) H, W, K] over the
+    transform codes `codes` (data/augment.py tta_codes: a power of two of them, the identity
+    last).  Per non-identity code: the augmenting gather loads the transformed batch, the
+    evaluation plan runs, tta_acc brings `prob` back by the inverse code into the accumulator
+    (the first writes it, the others add).  The identity pass goes through the same gather,
+    then tta_finish forms the mean in place.  Afterwards `prob` holds the mean, `target` the
+    stored target and `sums` the sums of the mean (BCE from the probabilities), so
+    `case_stats`, `case_surface` and `probs()` work unchanged."""
+    from ..data.augment import inverse_code
+    if e._dry:
+        raise RuntimeError("executor built with dry_run=True: evaluate_tta is validated, not launched")
+    codes = tuple(int(c) for c in codes)
+    M = len(codes)
+    if M < 2 or M & (M - 1) or codes[-1] != 0 or 0 in codes[:-1] or len(set(codes)) != M:
+        raise ValueError("evaluate_tta: a power of two >= 2 of distinct codes with the identity last, got %r"
+                         % (codes,))
+    if x.shape[0] != e.B:
+        raise ValueError("evaluate_tta takes the executor's batch of %d samples, got %d" % (e.B, x.shape[0]))
+    if getattr(e, "tta_plan", None) is None:
+        plan_tta(e, "f32_tta_finish" if e.dtype == "fp32" else "tta_finish")
+    # (inputs that are not fp32 / contiguous / on the device are converted first)
+    x = x.to(e.device, torch.float32).contiguous()
+    y = y.to(e.device, torch.float32).contiguous()
+    rows = e._tta_rows.get(codes)
+    if rows is None:
+        rows = e._tta_rows[codes] = torch.tensor(codes, dtype=torch.int32).view(M, 1).repeat(1, e.B).to(e.device)
+    if getattr(e, "_iota", None) is None:
+        e._iota = torch.arange(e.B, device=e.device, dtype=torch.int64)
+    s, dt = native.stream_handle(stream), getattr(e, "dt_id", 0)
+    ptrs, ints = e._tta_acc_args
+    for i, c in enumerate(codes):
+        e.load_indexed(x, y, e._iota, stream, aug=(rows[i], None))
+        e.evaluate_batch(stream)
+        if c:
+            e.C.generic("tta_acc", ptrs, ints + [inverse_code(c), 1 if i else 0], [], s, dt)
+    e.C.generic(e._tta_finish_kind, e._tta_finish_args[0], e._tta_finish_args[1], [1.0 / M], s, dt)

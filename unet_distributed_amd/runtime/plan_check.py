@@ -114,7 +114,19 @@ def _generic_write_spans(kind: str, p: List[int], ints: List[int]) -> List[Tuple
         B, D, H, W, _, cpad, K = ints[:7]
         eb = 4 if kind.startswith("f32") else 2
         return [(p[5], B * D * H * W * cpad * eb), (p[6], B * D * H * W * K * eb)]
+    # test-time augmentation: the fp32 accumulator (N, D, H, W, K in ints); the finish (total
+    # elements in ints) rewrites prob and writes one row of 4 floats per block and the 4 sums
+    if kind == "tta_acc" and len(p) > 1 and len(ints) >= 5:
+        N, D, H, W, K = ints[:5]
+        return [(p[1], N * D * H * W * K * 4)]
+    if kind in ("tta_finish", "f32_tta_finish") and len(p) > 4 and len(ints) >= 1:
+        return [(p[0], ints[0] * 4), (p[3], tta_finish_blocks(ints[0]) * 4 * 4), (p[4], 4 * 4)]
     return []
+
+
+def tta_finish_blocks(total: int) -> int:
+    """Blocks of a tta_finish launch (mirrors csrc/kernels/tta.hip)."""
+    return max(1, min(-(-(total // 4) // 256), 1024))
 
 
 def seg_stats_chunks(N: int, S: int, K: int) -> int:
@@ -187,6 +199,10 @@ def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], Li
         return _sel(p, [0, 1]), _sel(p, [2, 3])
     if kind in ("gather_batch_aug", "f32_gather_batch_aug"):
         return [q for q in _sel(p, [0, 1, 2, 3, 4]) if q], _sel(p, [5, 6])
+    if kind == "tta_acc":                # (write mode reads no element of the accumulator)
+        return _sel(p, [0, 1] if len(ints) > 6 and ints[6] else [0]), _sel(p, [1])
+    if kind in ("tta_finish", "f32_tta_finish"):
+        return _sel(p, [0, 1, 2]), _sel(p, [0, 3, 4])
     if kind == "tconv_compose":
         return _sel(p, [0, 1]), _sel(p, [2])
     if kind == "tconv_chain":
@@ -305,7 +321,7 @@ def engine_regions(e) -> Tuple[_Regions, set]:
             inputs.add("stat:" + k)
     for k in ("prob", "target", "sums", "head_partial", "head_ws", "slab", "bias_slab", "red_stage", "arena",
               "loss_scale_dev", "_no_dy", "case_stats_buf", "case_stats_partial",
-              "case_surface_buf", "case_surface_scratch"):
+              "case_surface_buf", "case_surface_scratch", "tta_acc_buf", "tta_partial"):
         R.add(k, getattr(e, k, None))
     inputs |= {"target", "arena", "loss_scale_dev", "_no_dy"}
     for k, t in getattr(e, "state", {}).items():
@@ -380,6 +396,23 @@ def check_stats_plan(e) -> List[str]:
     if e.stats_plan is None:
         return [e._case_stats_err]
     return check_plan(e, e.stats_plan, False, extra_inputs=("prob",))
+
+
+def check_tta_plan(e) -> List[str]:
+    """Errors of executor `e`'s test-time augmentation ops (`tta_plan`, built on first use or
+    with --eval_tta): a tta_acc that writes the accumulator, one that adds to it and the
+    finish.  They read the probabilities the evaluation plan left behind and the loaded
+    target; the accumulator must be the size of `prob` and the partial buffer hold one row
+    per block of the finish."""
+    if getattr(e, "tta_plan", None) is None:
+        return ["evaluate_tta is not planned (plan_tta)"]
+    errs = check_plan(e, e.tta_plan, False, extra_inputs=("prob",))
+    if e.tta_acc_buf.numel() != e.prob.numel() or e.tta_acc_buf.dtype != torch.float32:
+        errs.append("evaluate_tta: tta_acc_buf holds %d floats, prob %d" % (e.tta_acc_buf.numel(), e.prob.numel()))
+    need = tta_finish_blocks(e.prob.numel()) * 4
+    if e.tta_partial.numel() < need:
+        errs.append("evaluate_tta: tta_partial holds %d floats, %d needed" % (e.tta_partial.numel(), need))
+    return errs
 
 
 def check_surface_plan(e) -> List[str]:

@@ -24,9 +24,9 @@ import numpy as np
 import torch
 
 from .. import settings
-from ..config import parse_augment
+from ..config import parse_augment, parse_tta
 from ..data import datasets
-from ..data.augment import make_aug
+from ..data.augment import make_aug, tta_codes
 from ..data.loader import DeviceFeeder
 from ..models import reference
 from ..models.spec import spec_from_config
@@ -226,6 +226,9 @@ class Trainer:
                 names = parse_augment(cfg.augment)
                 print("Training augmentation: %s%s" % (", ".join(names), " (amplitude %g)" % cfg.augment_intensity
                                                        if "intensity" in names else ""))
+            if cfg.eval_tta:
+                print("Evaluation TTA: %s (%d passes)" % (", ".join(parse_tta(cfg.eval_tta)),
+                                                          len(tta_codes(cfg.eval_tta, cfg.dims))))
 
     def _batch(self, idx: np.ndarray, step: int = 0):
         # native backend + resident data: the backend gathers the batch itself (one
@@ -247,7 +250,10 @@ class Trainer:
         (their mean over classes) and `cases`.  A full batch costs one more launch on the
         forward its `eval_sums` ran; the `n % B` tail is one padded `eval_stats` call on
         rank `nbatches % world`.  With `--eval_hd95` the same cases also give `per_class["hd95"]`
-        and `hd95` (voxels; `last_eval_surface` per full batch, `eval_surface` for the tail)."""
+        and `hd95` (voxels; `last_eval_surface` per full batch, `eval_surface` for the tail).
+        With `--eval_tta` every one of these forwards is the backend's mean over the transforms
+        (the loss term of the batch metrics is then the BCE of the mean probabilities) and the
+        dict carries `tta`, the number of passes."""
         n = len(self.x_test)
         B = self.per_rank
         nbatches = n // B
@@ -303,6 +309,8 @@ class Trainer:
             hm95 = seg_metrics.hd95_metrics({"hd95_sum": cls[6 * K + 1:7 * K + 1], "cases": cls[6 * K]})
             m["per_class"]["hd95"] = hm95["hd95"]
             m["hd95"] = hm95["hd95_mean"]
+        if self.cfg.eval_tta:                   # every forward above was the mean over this many passes
+            m["tta"] = len(tta_codes(self.cfg.eval_tta, self.cfg.dims))
         return m
 
     # ------------------------------------------------------------------ step

@@ -45,12 +45,14 @@ def main(argv=None) -> float:
                    help="also print per-class case Dice, sensitivity and specificity (thresholded at 0.5)")
     p.add_argument("--hd95", action="store_true",
                    help="also print the per-class 95th-percentile Hausdorff distance in voxels (thresholded at 0.5)")
+    p.add_argument("--tta", default="", metavar="SPEC",
+                   help="test-time augmentation: score the mean prediction over flip and / or rot90 (comma-separated)")
     p.add_argument("--synthetic", type=int, default=0, metavar="N",
                    help="use N synthetic test slices instead of the .npy files")
     a = p.parse_args(argv)
     from .inference import load_saved_model
     print("Loading trained model from directory {}".format(a.export_dir))
-    model = load_saved_model(a.export_dir, device=a.device, batch=a.batch_size, backend=a.backend)
+    model = load_saved_model(a.export_dir, device=a.device, batch=a.batch_size, backend=a.backend, tta=a.tta)
     print('-' * 38)
     print('Loading and preprocessing test data...')
     print('-' * 38)
