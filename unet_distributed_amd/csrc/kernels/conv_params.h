@@ -301,6 +301,17 @@ struct PackSeg {
   long long dg_off;    // dgrad copy, -1 = none
 };
 
+// Geometry of one sliding-window launch (sliding.h): images [N][D][H][W][C], tiles of
+// Td x Th x Tw at strides sd, sh, sw; n* tiles per axis; a batch of B slots holding the
+// tiles [t0, t0 + nt).
+struct SwGeo {
+  int N, D, H, W, C;   // C: channels of the images (extract) / classes K (blend)
+  int Td, Th, Tw;
+  int sd, sh, sw;
+  int nd, nh, nw;
+  int B, t0, nt;
+};
+
 }  // namespace unet_types
 
 namespace unet {

@@ -726,6 +726,39 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
       };
     return [=](hipStream_t s) { return A->tta_finish_launch(prob, acc, t, total, inv_m, part, sums, s); };
   }
+  if (kind == "sw_extract" || kind == "sw_blend") {
+    // sw_extract  ptrs: x_all (fp32 [N][D][H][W][C]), xb (fp32 [B][Td][Th][Tw][C])
+    // sw_blend    ptrs: prob (fp32 [B][Td][Th][Tw][K]), w (fp32 [Td][Th][Tw]), acc (fp32 [N][D][H][W][K])
+    // ints: N, D, H, W, C (sw_blend: K), Td, Th, Tw, sd, sh, sw, B, t0, nt (the batch's tiles [t0, t0 + nt))
+    const bool blend = kind == "sw_blend";
+    need(blend ? 3 : 2, 14, 0);
+    check_msg(sw_check(blend, I[0], I[1], I[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9], I[10], I[11], I[12],
+                       I[13]));
+    const SwGeo g = sw_geo(I.data());
+    for (int i = 0; i < (blend ? 3 : 2); ++i) {
+      if (!P[i]) throw std::invalid_argument(kind + ": null pointer");
+      if (P[i] & 3) throw std::invalid_argument(kind + ": pointers must be aligned to 4 bytes");
+    }
+    if (blend) {
+      const float *prob = (const float*)vp(0), *w = (const float*)vp(1);
+      float* acc = (float*)vp(2);
+      return [=](hipStream_t s) { return unet::sw_blend_launch(prob, w, acc, g, s); };
+    }
+    const float* xa = (const float*)vp(0);
+    float* xb = (float*)vp(1);
+    return [=](hipStream_t s) { return unet::sw_extract_launch(xa, xb, g, s); };
+  }
+  if (kind == "sw_finish") {
+    // ptrs: acc (fp32 [N][D][H][W][K], in place), wsum (fp32 [D][H][W])   ints: N, D, H, W, K
+    need(2, 5, 0);
+    check_msg(sw_finish_check(I[0], I[1], I[2], I[3], I[4]));
+    float* acc = (float*)vp(0);
+    const float* wsum = (const float*)vp(1);
+    if (!acc || !wsum) throw std::invalid_argument("sw_finish: acc / wsum required");
+    if ((P[0] | P[1]) & 3) throw std::invalid_argument("sw_finish: pointers must be aligned to 4 bytes");
+    const int n = (int)I[0], d = (int)I[1], h = (int)I[2], w = (int)I[3], K = (int)I[4];
+    return [=](hipStream_t s) { return unet::sw_finish_launch(acc, wsum, n, d, h, w, K, s); };
+  }
   if (kind == "norm_moments") {
     // ptrs: A, B, partial, S  ints: N, P, C    (S[n][2][C] = per-sample sums of A and A*B)
     need(4, 3, 0);

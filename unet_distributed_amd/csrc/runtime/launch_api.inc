@@ -126,6 +126,19 @@ hipError_t tta_acc_launch(const float* prob, float* acc, int N, int D, int H, in
 hipError_t tta_finish_launch(float* prob, const float* acc, const void* t, long long total, float inv_m,
                              float* partial, float* sums, hipStream_t s);
 
+// sliding-window inference (sliding.h; fp32 in and out): xb [B][Td][Th][Tw][C] = the tiles
+// [t0, t0 + nt) of x_all [N][D][H][W][C] (zeros elsewhere); acc [N][D][H][W][K] += w * prob of
+// those tiles in ascending tile order (a multiplication, then an addition); acc /= wsum [D][H][W].
+// sw_check: kind 0 extract, 1 blend; sw_geo: the SwGeo of the 14 integers sw_check accepted
+const char* sw_check(long long kind, long long N, long long D, long long H, long long W, long long C, long long Td,
+                     long long Th, long long Tw, long long sd, long long sh, long long sw, long long B, long long t0,
+                     long long nt);
+const char* sw_finish_check(long long N, long long D, long long H, long long W, long long K);
+SwGeo sw_geo(const long long* v);
+hipError_t sw_extract_launch(const float* x_all, float* xb, const SwGeo& g, hipStream_t s);
+hipError_t sw_blend_launch(const float* prob, const float* w, float* acc, const SwGeo& g, hipStream_t s);
+hipError_t sw_finish_launch(float* acc, const float* wsum, int N, int D, int H, int W, int K, hipStream_t s);
+
 int norm_blocks_per_sample(int N, int P);
 int sample_slices(int N);  // partial workspace of the finalize launchers: sample_slices(N) * 2 * C floats
 const char* norm_check(int C, int G);

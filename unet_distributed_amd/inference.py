@@ -14,7 +14,9 @@ probabilities.
 On a GPU the native HIP executor's inference plan runs (forward only, dropout
 off, fused head+sigmoid) at a fixed micro-batch; a short last batch is padded.
 Elsewhere, or for configs the native executor does not cover, the ATen
-reference forward runs.
+reference forward runs.  ``predict`` takes images of the model's input size;
+``predict_sliding`` / ``stats_sliding`` / ``surface_sliding`` take images of any spatial
+size (sliding-window inference, :mod:`unet_distributed_amd.ops.sliding`).
 """
 
 import json
@@ -109,8 +111,57 @@ class Predictor:
                                           threshold).long().cpu() for s in range(0, x.shape[0], step)]
         return torch.cat(outs).numpy()
 
+    # ------------------------------------------------------------------ images of any spatial size
+    def sliding_chunks(self, shape, max_bytes: int = 1 << 30):
+        """[(begin, end)] of the chunks of whole images that `predict_sliding` works in: as many
+        images [(D,) H, W, Cin] as keep a chunk's fp32 input and accumulator (Cin + K floats per
+        pixel) under `max_bytes`, at least one.  Tile numbering restarts per chunk."""
+        if len(shape) != self.spec.dims + 2 or shape[-1] != self.spec.in_channels:
+            raise ValueError("sliding window: images [n, %sH, W, %d], got shape %r"
+                             % ("D, " if self.spec.dims == 3 else "", self.spec.in_channels, tuple(shape)))
+        per = int(np.prod(shape[1:-1])) * (self.spec.in_channels + self.spec.n_cl_out) * 4
+        m = max(1, int(max_bytes) // per)
+        return [(s, min(shape[0], s + m)) for s in range(0, shape[0], m)]
 
-SIGNATURE = "intel_unet_brats_model"
+    def _sliding(self, x, overlap, blend, max_bytes, score):
+        from .ops import sliding
+        sliding.check_overlap(overlap)
+        sliding.check_blend(blend)
+        x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32))
+        outs = []
+        for s, t in self.sliding_chunks(tuple(x.shape), max_bytes):
+            outs.append(score(self.backend.predict_sliding(x[s:t].to(self.device), overlap, blend), s, t).cpu())
+        return torch.cat(outs).numpy()
+
+    @torch.no_grad()
+    def predict_sliding(self, x, overlap: float = 0.5, blend: str = "gaussian", max_bytes: int = 1 << 30) -> np.ndarray:
+        """Probabilities fp32 [n, (D,) H, W, K] of images x [n, (D,) H, W, Cin] of any spatial size
+        by sliding-window inference (`ops.sliding`): overlapping tiles of the model's size at
+        stride T - floor(overlap T), every tile through the forward (with `tta=` the mean over
+        the transforms), blended with `blend` weights (constant | gaussian) and divided by the
+        summed weights.  Native: tile extraction and blend are HIP kernels (kernels/sliding.h)."""
+        return self._sliding(x, overlap, blend, max_bytes, lambda p, s, t: p.float())
+
+    @torch.no_grad()
+    def stats_sliding(self, x, y, threshold: float = 0.5, overlap: float = 0.5, blend: str = "gaussian",
+                      max_bytes: int = 1 << 30) -> np.ndarray:
+        """``[n][K][6] = {I, St, Sp, TP, FP, FN}`` per (image, class) of `predict_sliding`'s
+        probabilities against the full-size target y [n, (D,) H, W, K]."""
+        y = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32))
+        return self._sliding(x, overlap, blend, max_bytes, lambda p, s, t: self.backend.sliding_stats(
+            p, y[s:t].to(self.device), threshold).double())
+
+    @torch.no_grad()
+    def surface_sliding(self, x, y, threshold: float = 0.5, overlap: float = 0.5, blend: str = "gaussian",
+                        max_bytes: int = 1 << 30) -> np.ndarray:
+        """int64 ``[n][K][4] = {mp, mt, q_lo, q_hi}`` per (image, class) of `predict_sliding`'s
+        probabilities against the full-size target y: the surface-distance integers of HD95."""
+        y = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32))
+        return self._sliding(x, overlap, blend, max_bytes, lambda p, s, t: self.backend.sliding_surface(
+            p, y[s:t].to(self.device), threshold).long())
+
+
+SIGNATURE ="intel_unet_brats_model"
 
 
 def _spec_from_pb(path: str):

@@ -15,6 +15,10 @@ last ``eval_sums`` scored (no second forward) and ``eval_stats(x, y, threshold)`
 With ``--eval_tta`` every one of these evaluation forwards (``predict`` too) is the mean of
 the probabilities over the flipped / rotated inputs (``data.augment.tta_mean_torch`` on
 ATen, the executors' ``evaluate_tta`` on the HIP path); training steps are untouched.
+``predict_sliding(x, overlap, blend)`` scores images of any spatial size by sliding-window
+inference (``ops.sliding``: the torch loop on ATen, the executors' ``predict_sliding`` with
+the sw_extract / sw_blend / sw_finish kernels on the HIP path); ``sliding_stats`` /
+``sliding_surface`` score its full-size result against a full-size target.
 """
 
 from typing import Callable, Optional
@@ -23,7 +27,7 @@ import torch
 
 from ..data.augment import tta_codes, tta_mean_torch
 from ..models import reference
-from ..ops import losses, seg_metrics
+from ..ops import losses, seg_metrics, sliding
 from .params import FlatParams
 
 
@@ -35,6 +39,7 @@ class TorchBackend:
         self.flat = flat
         self.cfg = cfg
         self.device = torch.device(device)
+        self.B = per_rank_batch               # (tiles per forward of predict_sliding)
         self.dtype = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[cfg.dtype]
         if self.device.type == "cpu" and self.dtype == torch.float16:
             self.dtype = torch.float32
@@ -140,6 +145,23 @@ class TorchBackend:
         if self.tta:
             return tta_mean_torch(self._predict1, x.to(self.device), self.tta)
         return self._predict1(x)
+
+    @torch.no_grad()
+    def predict_sliding(self, x, overlap: float = 0.5, blend: str = "gaussian") -> torch.Tensor:
+        """Probabilities fp32 [n, (D,) H, W, K] of images of any spatial size: `predict` on
+        overlapping tiles of the model's size, blended (`ops.sliding.sliding_predict_torch`)."""
+        T = sliding.tile_shape(self.cfg.img_size, self.spec.dims)
+        return sliding.sliding_predict_torch(self.predict, x.to(self.device), T, self.B, overlap, blend)
+
+    @torch.no_grad()
+    def sliding_stats(self, p, y, threshold: float = 0.5) -> torch.Tensor:
+        """[n][K][6] of full-size probabilities p (`predict_sliding`) against the target y."""
+        return seg_metrics.case_stats_torch(p, y.to(p.device).float(), threshold)
+
+    @torch.no_grad()
+    def sliding_surface(self, p, y, threshold: float = 0.5) -> torch.Tensor:
+        """[n][K][4] of full-size probabilities p (`predict_sliding`) against the target y."""
+        return seg_metrics.case_surface_torch(p, y.to(p.device).float(), threshold)
 
     def after_optimizer(self):
         pass
@@ -266,6 +288,26 @@ class NativeBackend:
         e = self.engine
         self._evaluate(x, torch.zeros(x.shape[:-1] + (self.spec.n_cl_out,), device=x.device))
         return e.probs().clone()
+
+    @torch.no_grad()
+    def predict_sliding(self, x, overlap: float = 0.5, blend: str = "gaussian") -> torch.Tensor:
+        """Probabilities fp32 [n, (D,) H, W, K] of images of any spatial size, on the device: the
+        executor's sliding-window path (`native_engine.run_predict_sliding`: sw_extract, the
+        evaluation forward -- with --eval_tta the mean over the transforms -- and sw_blend per
+        batch of tiles, then sw_finish).  The executor's buffer, overwritten by the next call."""
+        return self.engine.predict_sliding(x.to(self.engine.device), overlap, blend, self.tta)
+
+    @torch.no_grad()
+    def sliding_stats(self, p, y, threshold: float = 0.5) -> torch.Tensor:
+        """fp32 [n][K][6] of full-size probabilities p (`predict_sliding`) against the target y."""
+        from .native_engine import sliding_stats
+        return sliding_stats(self.engine, p, y, threshold)
+
+    @torch.no_grad()
+    def sliding_surface(self, p, y, threshold: float = 0.5) -> torch.Tensor:
+        """int32 [n][K][4] of full-size probabilities p (`predict_sliding`) against the target y."""
+        from .native_engine import sliding_surface
+        return sliding_surface(self.engine, p, y, threshold)
 
     def adam_step(self, lr, b1p, b2p, grad_scale=1.0):
         self.engine.adam_step(lr, b1p, b2p, grad_scale)

@@ -35,7 +35,7 @@ import torch
 from .. import native
 from ..models.spec import UNetSpec
 from .native_engine import (gather_aug_args, plan_case_stats, plan_case_surface, plan_tta, run_case_stats,
-                            run_case_surface, run_evaluate_tta)
+                            run_case_surface, run_evaluate_tta, run_predict_sliding)
 from .params import FlatParams
 from .plan_check import RecordingPlan
 
@@ -90,6 +90,7 @@ class NativeUNetF32:
         self.tta_plan = self.tta_acc_buf = self.tta_partial = None
         if eval_tta:             # (otherwise on the first evaluate_tta call)
             plan_tta(self, "f32_tta_finish")
+        self.sw_plan = None      # (sliding-window inference: on the first predict_sliding call, or plan_sliding)
         self._adam_segs()
 
     # ------------------------------------------------------------------ shapes / buffers
@@ -449,3 +450,9 @@ class NativeUNetF32:
         (`data.augment.tta_codes`): `prob` then holds the mean, `target` the stored target and
         `sums` the sums of that mean (tta.h, `native_engine.run_evaluate_tta`)."""
         return run_evaluate_tta(self, x, y, codes, stream)
+
+    def predict_sliding(self, x: torch.Tensor, overlap: float = 0.5, blend: str = "gaussian", tta_codes=(),
+                        stream=None) -> torch.Tensor:
+        """Sliding-window probabilities fp32 [N, (D,) H, W, 1] of device images of any spatial
+        size (`native_engine.run_predict_sliding`, kernels/sliding.h): the executor's buffer."""
+        return run_predict_sliding(self, x, overlap, blend, tta_codes, stream)

@@ -301,6 +301,7 @@ class NativeUNet:
         self.tta_plan = self.tta_acc_buf = self.tta_partial = None
         if eval_tta:             # (otherwise on the first evaluate_tta call)
             plan_tta(self, "tta_finish")
+        self.sw_plan = None      # (sliding-window inference: on the first predict_sliding call, or plan_sliding)
         if not dry_run:          # dry_run: plan construction only (CPU tests, no GPU launches)
             self.repack()
 
@@ -2185,6 +2186,12 @@ class NativeUNet:
         probabilities, `target` the stored target and `sums` the sums of that mean."""
         return run_evaluate_tta(self, x, y, codes, stream)
 
+    def predict_sliding(self, x: torch.Tensor, overlap: float = 0.5, blend: str = "gaussian", tta_codes=(),
+                        stream=None) -> torch.Tensor:
+        """Sliding-window probabilities fp32 [N, (D,) H, W, K] of device images of any spatial
+        size (`run_predict_sliding`, kernels/sliding.h): the executor's buffer."""
+        return run_predict_sliding(self, x, overlap, blend, tta_codes, stream)
+
 
 def gather_aug_args(e, x_all, y_all, idx, aug, cin: int, cpad: int, K: int):
     """(ptrs, ints) of an executor's gather_batch_aug / f32_gather_batch_aug launch
@@ -2373,3 +2380,126 @@ def run_evaluate_tta(e, x: torch.Tensor, y: torch.Tensor, codes, stream=None) ->
         if c:
             e.C.generic("tta_acc", ptrs, ints + [inverse_code(c), 1 if i else 0], [], s, dt)
     e.C.generic(e._tta_finish_kind, e._tta_finish_args[0], e._tta_finish_args[1], [1.0 / M], s, dt)
+
+
+def plan_sliding(e) -> None:
+    """Buffers and the validation plan of an executor's `predict_sliding` (kernels/sliding.h,
+    `ops.sliding` is the definition): the fp32 staging batch `sw_x` of B tiles of the model's
+    size that `sw_extract` fills and the plain load consumes, the zero target that rides
+    along, and the device weight maps `sw_w` [constant, gaussian].  Like `case_stats` the ops
+    are in neither `plan` nor `eval_plan`: `sw_plan` holds the ops of a probe geometry -- one
+    image a quarter tile wider than the tile at overlap 0.5, two tiles with the second clamped
+    -- for the static plan validation; the accumulator and summed weights of a real call
+    are made per geometry by `run_predict_sliding`."""
+    from ..ops import sliding
+    K, cin = getattr(e, "K", 1), e.spec.in_channels
+    T = e.sdims(1)
+    sp = T if e.dims == 3 else T[1:]
+    e.sw_x = torch.zeros((e.B,) + sp + (cin,), dtype=torch.float32, device=e.device)
+    e.sw_y = torch.zeros((e.B,) + sp + (K,), dtype=torch.float32, device=e.device)
+    e.sw_w = torch.stack([sliding.weight_map(T, b) for b in sliding.BLENDS]).to(e.device)
+    e._sw_run = None
+    dims = (T[0], T[1], T[2] + max(1, T[2] // 4))
+    stride = sliding.strides(T, 0.5)
+    e.sw_src = torch.zeros((1,) + dims + (cin,), dtype=torch.float32, device=e.device)
+    e.sw_acc = torch.zeros((1,) + dims + (K,), dtype=torch.float32, device=e.device)
+    e.sw_wsum = sliding.weight_sum(dims, T, stride, "gaussian").to(e.device)
+    e.sw_plan = RecordingPlan(e.C.Plan(getattr(e, "dt_id", 0)))
+    total = sliding.tiles_per_image(dims, T, stride)
+    for t0 in range(0, total, e.B):
+        tail = list(T) + list(stride) + [e.B, t0, min(e.B, total - t0)]
+        e.sw_plan.add_generic("sw_extract", [_ptr(e.sw_src), _ptr(e.sw_x)], [1] + list(dims) + [cin] + tail, [],
+                              "sw_extract:%d" % t0)
+        e.sw_plan.add_generic("sw_blend", [_ptr(e.prob), _ptr(e.sw_w[1]), _ptr(e.sw_acc)],
+                              [1] + list(dims) + [K] + tail, [], "sw_blend:%d" % t0)
+    e.sw_plan.add_generic("sw_finish", [_ptr(e.sw_acc), _ptr(e.sw_wsum)], [1] + list(dims) + [K], [], "sw_finish")
+
+
+def run_predict_sliding(e, x_dev: torch.Tensor, overlap: float = 0.5, blend: str = "gaussian", tta_codes=(),
+                        stream=None) -> torch.Tensor:
+    """Sliding-window probabilities of the images x_dev [N, (D,) H, W, Cin] of any spatial size
+    (`ops.sliding`): zero the accumulator; per batch of B tiles `sw_extract` fills the staging
+    batch, the evaluation forward runs on it (the plain load and plan, or `evaluate_tta` over
+    `tta_codes`) and `sw_blend` adds the weighted probabilities; `sw_finish` divides by the
+    summed weights.  Everything is issued in order on one stream, so every pixel's sum runs
+    in ascending tile order, as the oracle's.  Returns fp32 [N, (D,) H, W, K] on the device:
+    the executor's buffer, overwritten by the next call of the same geometry."""
+    from ..ops import sliding
+    if e._dry:
+        raise RuntimeError("executor built with dry_run=True: predict_sliding is validated, not launched")
+    sliding.check_blend(blend)
+    T = e.sdims(1)
+    stride = sliding.strides(T, overlap)
+    K, cin = getattr(e, "K", 1), e.spec.in_channels
+    if x_dev.dim() != e.dims + 2 or x_dev.shape[-1] != cin or x_dev.shape[0] < 1:
+        raise ValueError("predict_sliding: images [n, %sH, W, %d], got shape %r"
+                         % ("D, " if e.dims == 3 else "", cin, tuple(x_dev.shape)))
+    if getattr(e, "sw_plan", None) is None:
+        plan_sliding(e)
+    x = x_dev.to(e.device, torch.float32).contiguous()
+    N = x.shape[0]
+    dims = tuple(x.shape[1:4]) if e.dims == 3 else (1,) + tuple(x.shape[1:3])
+    key = (N, dims, stride, blend)
+    run = e._sw_run
+    if run is None or run["key"] != key:
+        e._sw_run = None                      # (the previous geometry's buffers go first)
+        run = e._sw_run = dict(key=key, acc=torch.empty((N,) + dims + (K,), dtype=torch.float32, device=e.device),
+                               wsum=sliding.weight_sum(dims, T, stride, blend).to(e.device))
+    acc, w = run["acc"], e.sw_w[sliding.BLENDS.index(blend)]
+    total = N * sliding.tiles_per_image(dims, T, stride)
+    s, dt = native.stream_handle(stream), getattr(e, "dt_id", 0)
+    with torch.cuda.stream(stream) if stream is not None else _nullctx():
+        acc.zero_()
+    head = [N] + list(dims)
+    for t0 in range(0, total, e.B):
+        tail = list(T) + list(stride) + [e.B, t0, min(e.B, total - t0)]
+        e.C.generic("sw_extract", [_ptr(x), _ptr(e.sw_x)], head + [cin] + tail, [], s, dt)
+        if tta_codes:
+            e.evaluate_tta(e.sw_x, e.sw_y, tta_codes, stream)
+        else:
+            e.load_batch(e.sw_x, e.sw_y, stream)
+            e.evaluate_batch(stream)
+        e.C.generic("sw_blend", [_ptr(e.prob), _ptr(w), _ptr(acc)], head + [K] + tail, [], s, dt)
+    e.C.generic("sw_finish", [_ptr(acc), _ptr(run["wsum"])], head + [K], [], s, dt)
+    return acc if e.dims == 3 else acc.view((N,) + dims[1:] + (K,))
+
+
+def sliding_stats(e, prob: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, stream=None) -> torch.Tensor:
+    """[N][K][6] = {I, St, Sp, TP, FP, FN} per (image, class) of full-size probabilities
+    prob [N, (D,) H, W, K] (`run_predict_sliding`'s result) against the fp32 target y of the
+    same shape: the `f32_seg_stats` op at the images' own size (fp32), or `case_stats_torch` on
+    the device (float64) where the op refuses the shape (S % 8, S >= 2^24, N S K >= 2^31)."""
+    from ..ops import seg_metrics
+    prob, y = prob.contiguous(), y.to(prob.device, torch.float32).contiguous()
+    N, K = prob.shape[0], prob.shape[-1]
+    S = prob[0].numel() // K
+    try:
+        chunks = e.C.seg_stats_chunks(N, S, K)
+    except ValueError:
+        return seg_metrics.case_stats_torch(prob, y, threshold)
+    out = torch.zeros(N, K, 6, dtype=torch.float32, device=prob.device)
+    part = torch.zeros(max(1, N * chunks * 6 * K), dtype=torch.float32, device=prob.device)
+    e.C.generic("f32_seg_stats", [_ptr(prob), _ptr(y), _ptr(out), _ptr(part)], [N, S, K], [float(threshold)],
+                native.stream_handle(stream), 0)
+    return out
+
+
+def sliding_surface(e, prob: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, stream=None) -> torch.Tensor:
+    """int32 [N][K][4] = {mp, mt, q_lo, q_hi} per (image, class) of full-size probabilities
+    against the fp32 target y: `f32_surf_dist` at the images' own size in groups that fit
+    SURF_SCRATCH_CAP, or `case_surface_torch` on the device where the op refuses the shape."""
+    from ..ops import seg_metrics
+    prob, y = prob.contiguous(), y.to(prob.device, torch.float32).contiguous()
+    N, K = prob.shape[0], prob.shape[-1]
+    d, h, w = tuple(prob.shape[1:4]) if prob.dim() == 5 else (1,) + tuple(prob.shape[1:3])
+    try:
+        one = e.C.surf_dist_scratch(1, d, h, w, K)
+        e.C.surf_dist_scratch(N, d, h, w, K)
+        group = surf_dist_group(N, one, max(one, min(one * N, SURF_SCRATCH_CAP)))
+    except ValueError:
+        return seg_metrics.case_surface_torch(prob, y, threshold).to(torch.int32)
+    out = torch.zeros(N, K, 4, dtype=torch.int32, device=prob.device)
+    scratch = torch.empty(one * group // 4, dtype=torch.int32, device=prob.device)
+    launch_surf_dist(e.C, "f32_surf_dist", [_ptr(prob), _ptr(y), _ptr(out), _ptr(scratch)], [N, d, h, w, K],
+                     threshold, scratch.numel() * 4, 4, native.stream_handle(stream), 0)
+    return out

@@ -121,6 +121,18 @@ def _generic_write_spans(kind: str, p: List[int], ints: List[int]) -> List[Tuple
         return [(p[1], N * D * H * W * K * 4)]
     if kind in ("tta_finish", "f32_tta_finish") and len(p) > 4 and len(ints) >= 1:
         return [(p[0], ints[0] * 4), (p[3], tta_finish_blocks(ints[0]) * 4 * 4), (p[4], 4 * 4)]
+    # sliding window (N, D, H, W, C | K, Td, Th, Tw, sd, sh, sw, B, t0, nt in ints): the staging
+    # batch; the accumulator up to the end of the last image the batch touches; the whole accumulator
+    if kind == "sw_extract" and len(p) > 1 and len(ints) >= 14:
+        return [(p[1], ints[11] * ints[5] * ints[6] * ints[7] * ints[4] * 4)]
+    if kind == "sw_blend" and len(p) > 2 and len(ints) >= 14:
+        from ..ops.sliding import tiles_per_image
+        tpi = tiles_per_image(ints[1:4], ints[5:8], ints[8:11])
+        last = (ints[12] + ints[13] - 1) // tpi
+        return [(p[2], (last + 1) * ints[1] * ints[2] * ints[3] * ints[4] * 4)]
+    if kind == "sw_finish" and len(p) > 1 and len(ints) >= 5:
+        N, D, H, W, K = ints[:5]
+        return [(p[0], N * D * H * W * K * 4)]
     return []
 
 
@@ -203,6 +215,12 @@ def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], Li
         return _sel(p, [0, 1] if len(ints) > 6 and ints[6] else [0]), _sel(p, [1])
     if kind in ("tta_finish", "f32_tta_finish"):
         return _sel(p, [0, 1, 2]), _sel(p, [0, 3, 4])
+    if kind == "sw_extract":
+        return _sel(p, [0]), _sel(p, [1])
+    if kind == "sw_blend":
+        return _sel(p, [0, 1, 2]), _sel(p, [2])
+    if kind == "sw_finish":
+        return _sel(p, [0, 1]), _sel(p, [0])
     if kind == "tconv_compose":
         return _sel(p, [0, 1]), _sel(p, [2])
     if kind == "tconv_chain":
@@ -321,7 +339,8 @@ def engine_regions(e) -> Tuple[_Regions, set]:
             inputs.add("stat:" + k)
     for k in ("prob", "target", "sums", "head_partial", "head_ws", "slab", "bias_slab", "red_stage", "arena",
               "loss_scale_dev", "_no_dy", "case_stats_buf", "case_stats_partial",
-              "case_surface_buf", "case_surface_scratch", "tta_acc_buf", "tta_partial"):
+              "case_surface_buf", "case_surface_scratch", "tta_acc_buf", "tta_partial",
+              "sw_src", "sw_x", "sw_w", "sw_acc", "sw_wsum"):
         R.add(k, getattr(e, k, None))
     inputs |= {"target", "arena", "loss_scale_dev", "_no_dy"}
     for k, t in getattr(e, "state", {}).items():
@@ -412,6 +431,23 @@ def check_tta_plan(e) -> List[str]:
     need = tta_finish_blocks(e.prob.numel()) * 4
     if e.tta_partial.numel() < need:
         errs.append("evaluate_tta: tta_partial holds %d floats, %d needed" % (e.tta_partial.numel(), need))
+    return errs
+
+
+def check_sliding_plan(e) -> List[str]:
+    """Errors of executor `e`'s sliding-window ops (`sw_plan`, built by `plan_sliding` on first
+    use): per batch of its probe geometry an sw_extract into the staging batch and an sw_blend
+    of the probabilities the evaluation plan leaves behind, then the sw_finish.  The probe
+    images, the weight maps and the summed weights are inputs; the accumulator is zeroed
+    before the first batch.  The staging batch must hold one batch of fp32 tiles and the
+    accumulator every image of the probe."""
+    if getattr(e, "sw_plan", None) is None:
+        return ["predict_sliding is not planned (plan_sliding)"]
+    errs = check_plan(e, e.sw_plan, False, extra_inputs=("prob", "sw_src", "sw_w", "sw_wsum", "sw_acc"))
+    d, h, w = e.sdims(1)
+    need = e.B * d * h * w * e.spec.in_channels
+    if e.sw_x.numel() != need or e.sw_x.dtype != torch.float32:
+        errs.append("predict_sliding: sw_x holds %d floats, a batch of tiles %d" % (e.sw_x.numel(), need))
     return errs
 
 

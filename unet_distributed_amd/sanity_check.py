@@ -49,7 +49,19 @@ def main(argv=None) -> float:
                    help="test-time augmentation: score the mean prediction over flip and / or rot90 (comma-separated)")
     p.add_argument("--synthetic", type=int, default=0, metavar="N",
                    help="use N synthetic test slices instead of the .npy files")
+    p.add_argument("--synthetic_size", type=int, default=0, metavar="S",
+                   help="side of the --synthetic images (default: the model's input size; "
+                        "another size needs --sliding)")
+    p.add_argument("--sliding", action="store_true",
+                   help="sliding-window inference: the test images may have any spatial size "
+                        "(overlapping tiles of the model's size, blended); covers every sample, as --all_batches")
+    p.add_argument("--overlap", type=float, default=0.5, metavar="F",
+                   help="--sliding: fraction of a tile shared with its neighbour, 0 .. 0.75")
+    p.add_argument("--blend", default="gaussian", choices=["constant", "gaussian"],
+                   help="--sliding: weights of a tile's pixels in the blend")
     a = p.parse_args(argv)
+    if not 0.0 <= a.overlap <= 0.75:
+        p.error("--overlap must lie in [0, 0.75], got %r" % a.overlap)
     from .inference import load_saved_model
     print("Loading trained model from directory {}".format(a.export_dir))
     model = load_saved_model(a.export_dir, device=a.device, batch=a.batch_size, backend=a.backend, tta=a.tta)
@@ -57,17 +69,27 @@ def main(argv=None) -> float:
     print('Loading and preprocessing test data...')
     print('-' * 38)
     if a.synthetic:
-        x, y = datasets.synthetic_brats(a.synthetic, model.img_size, model.spec.in_channels, model.spec.dims, seed=1,
-                                        out_channels=model.spec.n_cl_out)
+        if a.synthetic_size and a.synthetic_size != model.img_size and not a.sliding:
+            p.error("--synthetic_size %d differs from the model's input size %d: add --sliding"
+                    % (a.synthetic_size, model.img_size))
+        x, y = datasets.synthetic_brats(a.synthetic, a.synthetic_size or model.img_size, model.spec.in_channels,
+                                        model.spec.dims, seed=1, out_channels=model.spec.n_cl_out)
     else:
         xi, yi = datasets.load_data(a.data_path, "_test")
         x, y = datasets.update_channels(xi, yi, a.in_channels, a.out_channels, a.mode)
+    # --sliding: the same loops through the sliding-window methods (images of any spatial size),
+    # over every sample (the reference's iteration, which drops the tail, is kept for its own flow)
+    every = a.all_batches or a.sliding
+    sw = dict(overlap=a.overlap, blend=a.blend)
+    predict = (lambda v: model.predict_sliding(v, **sw)) if a.sliding else model.predict
+    stats_of = (lambda v, t: model.stats_sliding(v, t, **sw)) if a.sliding else model.stats
+    surface_of = (lambda v, t: model.surface_sliding(v, t, **sw)) if a.sliding else model.surface
     dice, nb = 0.0, 0
     t0 = time.time()
-    for s in batch_starts(len(x), a.batch_size, a.all_batches):
+    for s in batch_starts(len(x), a.batch_size, every):
         xb = np.asarray(x[s:s + a.batch_size], dtype=np.float32)
         yb = np.asarray(y[s:s + a.batch_size], dtype=np.float32)
-        pb = model.predict(xb)
+        pb = predict(xb)
         dice += sanity_dice(yb, pb)
         nb += 1
     dt = time.time() - t0
@@ -77,9 +99,9 @@ def main(argv=None) -> float:
         # (outside the timed loop: the same samples, thresholded at 0.5)
         from .ops import seg_metrics
         K = model.spec.n_cl_out
-        stats = [model.stats(np.asarray(x[s:s + a.batch_size], dtype=np.float32),
-                             np.asarray(y[s:s + a.batch_size], dtype=np.float32))
-                 for s in batch_starts(len(x), a.batch_size, a.all_batches)]
+        stats = [stats_of(np.asarray(x[s:s + a.batch_size], dtype=np.float32),
+                          np.asarray(y[s:s + a.batch_size], dtype=np.float32))
+                 for s in batch_starts(len(x), a.batch_size, every)]
         m = seg_metrics.metrics_from_case_stats(np.concatenate(stats), int(np.prod(y.shape[1:])) // K)
         for k in range(K):
             print("class {}: case Dice = {}, sensitivity = {}, specificity = {}".format(
@@ -88,9 +110,9 @@ def main(argv=None) -> float:
         print("Case Dice = {} ({} cases)".format(seg_metrics.fmt(m["case_dice_mean"]), m["cases"]))
     if a.hd95 and nb:
         from .ops import seg_metrics
-        surf = [model.surface(np.asarray(x[s:s + a.batch_size], dtype=np.float32),
-                              np.asarray(y[s:s + a.batch_size], dtype=np.float32))
-                for s in batch_starts(len(x), a.batch_size, a.all_batches)]
+        surf = [surface_of(np.asarray(x[s:s + a.batch_size], dtype=np.float32),
+                           np.asarray(y[s:s + a.batch_size], dtype=np.float32))
+                for s in batch_starts(len(x), a.batch_size, every)]
         m = seg_metrics.hd95_metrics(seg_metrics.accumulate_hd95(np.concatenate(surf), tuple(y.shape[1:-1])))
         for k in range(len(m["hd95"])):
             print("class {}: HD95 = {}".format(k, seg_metrics.fmt(m["hd95"][k])))
