@@ -106,6 +106,7 @@ class Config:
     augment: str = ""                # training batches only: comma-separated subset of flip, rot90, intensity
     augment_intensity: float = 0.1   # intensity: scale in [1-a, 1+a], shift in [-a, a] per (sample, channel)
     eval_tta: str = ""               # evaluation only: mean prediction over flip and / or rot90 (comma-separated)
+    eval_components: str = ""        # evaluation only: connected-component filter, comma list of largest, min:V
 
     @property
     def method_up(self):
@@ -160,6 +161,31 @@ def parse_tta(s: str) -> tuple:
     return tuple(names)
 
 
+def parse_components(s: str) -> tuple:
+    """The --eval_components string as the policy (keep_largest, min_size): a comma list of
+    `largest` and / or `min:V` (V >= 1 voxels); "" is (False, 0), the filter off.  An unknown,
+    malformed or repeated item is a SystemExit that names it."""
+    items = [t.strip() for t in str(s).split(",")] if str(s).strip() else []
+    largest, min_size, seen = False, 0, []
+    for t in items:
+        name = t.split(":", 1)[0]
+        if t == "largest":
+            largest = True
+        elif name == "min" and ":" in t:
+            v = t.split(":", 1)[1].strip()
+            if not v.isdigit() or int(v) < 1:
+                raise SystemExit("--eval_components: min:V takes a voxel count V >= 1, got %r" % t)
+            if int(v) >= 1 << 31:
+                raise SystemExit("--eval_components: min:V below 2^31, got %r" % t)
+            min_size = int(v)
+        else:
+            raise SystemExit("--eval_components: unknown item %r (choose from largest, min:V)" % t)
+        if name in seen:
+            raise SystemExit("--eval_components: %r is listed twice" % name)
+        seen.append(name)
+    return largest, min_size
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(
         description="MI355X-native distributed UNet trainer "
@@ -207,6 +233,7 @@ def validate(cfg: Config) -> None:
         raise SystemExit("--eval_threshold must lie strictly inside (0, 1)")
     parse_augment(cfg.augment)
     parse_tta(cfg.eval_tta)
+    parse_components(cfg.eval_components)
     if not 0.0 <= cfg.augment_intensity < 1.0:
         raise SystemExit("--augment_intensity must be in [0, 1)")
     if cfg.mode == 5 and cfg.out_channels > 3:

@@ -759,6 +759,29 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
     const int n = (int)I[0], d = (int)I[1], h = (int)I[2], w = (int)I[3], K = (int)I[4];
     return [=](hipStream_t s) { return unet::sw_finish_launch(acc, wsum, n, d, h, w, K, s); };
   }
+  if (kind == "components") {
+    // ptrs: prob (fp32 [N][S][K]), out (fp32 [N][S][K]), info (int32 [N][K][4] = {components, kept
+    //       components, largest size, kept voxels}), scratch (components_scratch(N, D, H, W, K) bytes,
+    //       16-byte aligned)
+    // ints: N samples, D, H, W (D = 1: 2D), K classes, keep_largest (0 / 1), min_size   floats: threshold
+    need(4, 7, 1);
+    const float* prob = (const float*)vp(0);
+    float* out = (float*)vp(1);
+    int* info = (int*)vp(2);
+    int* scratch = (int*)vp(3);
+    check_msg(unet::components_check(I[0], I[1], I[2], I[3], I[4], I[6]));
+    if (I[5] != 0 && I[5] != 1) throw std::invalid_argument("components: keep_largest is 0 or 1");
+    const int n = (int)I[0], d = (int)I[1], h = (int)I[2], w = (int)I[3], K = (int)I[4];
+    const int largest = (int)I[5], min_size = (int)I[6];
+    const float thr = (float)F[0];
+    if (!(thr > 0.0f && thr < 1.0f)) throw std::invalid_argument("components: threshold in (0, 1)");
+    if (!prob || !out || !info) throw std::invalid_argument("components: prob / out / info required");
+    if ((P[0] | P[1] | P[2]) & 3) throw std::invalid_argument("components: pointers must be aligned to 4 bytes");
+    if (!scratch || (P[3] & 15)) throw std::invalid_argument("components: 16-byte aligned scratch buffer required");
+    return [=](hipStream_t s) {
+      return unet::components_launch(prob, n, d, h, w, K, thr, largest, min_size, scratch, out, info, s);
+    };
+  }
   if (kind == "norm_moments") {
     // ptrs: A, B, partial, S  ints: N, P, C    (S[n][2][C] = per-sample sums of A and A*B)
     need(4, 3, 0);
@@ -1136,6 +1159,16 @@ PYBIND11_MODULE(_C, m) {
     check_msg(surf_dist_check(N, D, H, W, K));
     return surf_dist_scratch(N, D, H, W, K);
   }, py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("K"));
+  // bytes of the scratch of a components launch over N samples (int32 label and size planes
+  // [N][K][S], sel [N][K] and the selection's parts, rounded up to 16); components_check: the reason a launch is refused, or None
+  m.def("components_scratch", [](long long N, long long D, long long H, long long W, long long K) {
+    check_msg(unet::components_check(N, D, H, W, K, 0));
+    return unet::components_scratch(N, D, H, W, K);
+  }, py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("K"));
+  m.def("components_check", [](long long N, long long D, long long H, long long W, long long K, long long min_size) {
+    const char* msg = unet::components_check(N, D, H, W, K, min_size);
+    return msg ? py::object(py::str(msg)) : py::object(py::none());
+  }, py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("K"), py::arg("min_size") = 0);
   m.def("norm_blocks_per_sample", &norm_blocks_per_sample);
   m.def("sample_slices", &sample_slices);
   m.def("row_slices", &row_slices);

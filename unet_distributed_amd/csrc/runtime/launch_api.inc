@@ -219,4 +219,12 @@ hipError_t f32_surf_dist_launch(const float* prob, const float* t, int N, int D,
 // tta_finish with an fp32 target (f32_tta.hip)
 hipError_t f32_tta_finish_launch(float* prob, const float* acc, const float* t, long long total, float inv_m,
                                  float* partial, float* sums, hipStream_t s);
+// connected-component filtering of thresholded probabilities (components.h, f32_components.hip):
+// prob, out fp32 [N][S][K], S = D H W; info int32 [N][K][4] = {components, kept components, largest
+// size, kept voxels} under the policy (keep_largest, min_size) at threshold thr; scratch:
+// components_scratch(N, D, H, W, K) bytes, 16-byte aligned, written before it is read
+const char* components_check(long long N, long long D, long long H, long long W, long long K, long long min_size);
+long long components_scratch(long long N, long long D, long long H, long long W, long long K);
+hipError_t components_launch(const float* prob, int N, int D, int H, int W, int K, float thr, int keep_largest,
+                             int min_size, int* scratch, float* out, int* info, hipStream_t s);
 hipError_t f32_transpose_launch(const float* src, int T, int A, int B, int flip, float* dst, hipStream_t s);

@@ -35,8 +35,10 @@ from .utils.checkpoint import tensors_to_flat
 class _Cfg:
     """Minimal config for the backends (inference needs no optimiser flags)."""
 
-    def __init__(self, img_size, dtype, eval_dropout=False, eval_tta=""):
+    def __init__(self, img_size, dtype, eval_dropout=False, eval_tta="", eval_components=""):
         self.eval_tta = eval_tta
+        self.eval_components = eval_components
+        self.eval_threshold = 0.5
         self.img_size = img_size
         self.dtype = dtype
         self.loss = "dice"
@@ -47,15 +49,21 @@ class _Cfg:
 
 class Predictor:
     def __init__(self, spec: UNetSpec, flat: FlatParams, img_size: int, device, batch: int,
-                 dtype: str = "bf16", backend: str = "auto", state=None, tta: str = ""):
+                 dtype: str = "bf16", backend: str = "auto", state=None, tta: str = "", components: str = ""):
         """`tta`: test-time augmentation, a comma list of flip and rot90 (the --eval_tta
-        spelling): `predict`, `stats` and `surface` then score the mean over the transforms."""
-        from .config import parse_tta
+        spelling): `predict`, `stats` and `surface` then score the mean over the transforms.
+        `components`: connected-component filter, a comma list of largest and min:V (the
+        --eval_components spelling): `predict` / `predict_sliding` then return the filtered
+        map (thresholded at 0.5), `stats` and `surface` score it and `components` /
+        `components_sliding` give the component counts."""
+        from .config import parse_components, parse_tta
         from .runtime.backends import NativeBackend, TorchBackend, resolve_backend
         self.spec, self.flat, self.batch, self.img_size = spec, flat, batch, img_size
         self.device = torch.device(device)
         parse_tta(tta)
-        cfg = _Cfg(img_size, dtype if self.device.type == "cuda" else "fp32", eval_tta=tta)
+        parse_components(components)
+        cfg = _Cfg(img_size, dtype if self.device.type == "cuda" else "fp32", eval_tta=tta,
+                   eval_components=components)
         if resolve_backend(backend, spec, cfg, self.device) == "native":
             from . import native
             native.require()
@@ -111,6 +119,17 @@ class Predictor:
                                           threshold).long().cpu() for s in range(0, x.shape[0], step)]
         return torch.cat(outs).numpy()
 
+    @torch.no_grad()
+    def components(self, x, threshold: float = 0.5) -> np.ndarray:
+        """int64 ``[n][K][4] = {components, kept components, largest size, kept voxels}`` per
+        (sample, class) for any n, of the `components=` policy (``ops.components``; native:
+        chunks of ``batch``, a short last chunk padded)."""
+        x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32))
+        step = self.batch if self.backend.name == "native" else max(1, x.shape[0])
+        outs = [self.backend.eval_components(x[s:s + step].to(self.device), None, threshold).long().cpu()
+                for s in range(0, x.shape[0], step)]
+        return torch.cat(outs).numpy()
+
     # ------------------------------------------------------------------ images of any spatial size
     def sliding_chunks(self, shape, max_bytes: int = 1 << 30):
         """[(begin, end)] of the chunks of whole images that `predict_sliding` works in: as many
@@ -161,6 +180,15 @@ class Predictor:
             p, y[s:t].to(self.device), threshold).long())
 
 
+    @torch.no_grad()
+    def components_sliding(self, x, threshold: float = 0.5, overlap: float = 0.5, blend: str = "gaussian",
+                           max_bytes: int = 1 << 30) -> np.ndarray:
+        """int64 ``[n][K][4]`` per (image, class) of the `components=` policy on `predict_sliding`'s
+        blended full-size probabilities."""
+        return self._sliding(x, overlap, blend, max_bytes, lambda p, s, t: self.backend.sliding_components(
+            p, threshold).long())
+
+
 SIGNATURE ="intel_unet_brats_model"
 
 
@@ -191,7 +219,7 @@ def _spec_from_json(path: str):
 
 
 def load_saved_model(export_dir: str, device=None, batch: int = 128, dtype: str = "bf16",
-                     backend: str = "auto", tta: str = "") -> Predictor:
+                     backend: str = "auto", tta: str = "", components: str = "") -> Predictor:
     pb = os.path.join(export_dir, "saved_model.pb")
     if os.path.exists(pb):
         spec, img_size = _spec_from_pb(pb)
@@ -204,4 +232,4 @@ def load_saved_model(export_dir: str, device=None, batch: int = 128, dtype: str 
     tensors_to_flat(flat, tensors, strict=True)
     state = {k: v for k, v in tensors.items() if k.endswith("moving_mean") or k.endswith("moving_variance")}
     return Predictor(spec, flat, int(img_size), device, batch, dtype=dtype, backend=backend, state=state,
-                     tta=tta)
+                     tta=tta, components=components)

@@ -19,6 +19,12 @@ ATen, the executors' ``evaluate_tta`` on the HIP path); training steps are untou
 inference (``ops.sliding``: the torch loop on ATen, the executors' ``predict_sliding`` with
 the sw_extract / sw_blend / sw_finish kernels on the HIP path); ``sliding_stats`` /
 ``sliding_surface`` score its full-size result against a full-size target.
+With ``--eval_components`` the per-case methods (``*_stats``, ``*_surface``) score the
+connected-component-filtered map (``ops.components``: the torch definition on ATen, the
+executors' ``components`` op on the HIP path), ``predict`` / ``predict_sliding`` return it and
+``last_eval_components`` / ``eval_components`` give its ``info`` rows; with --eval_tta the
+filter applies to the mean, with sliding windows to the blended full-size map.  ``eval_sums``
+never sees the filter.
 """
 
 from typing import Callable, Optional
@@ -27,6 +33,8 @@ import torch
 
 from ..data.augment import tta_codes, tta_mean_torch
 from ..models import reference
+from ..config import parse_components
+from ..ops import components as cc
 from ..ops import losses, seg_metrics, sliding
 from .params import FlatParams
 
@@ -55,9 +63,25 @@ class TorchBackend:
         self.bounds = list(bounds) if bounds else [flat.numel]
         # --eval_tta: the transform codes every evaluation forward is averaged over (() = off)
         self.tta = tta_codes(getattr(cfg, "eval_tta", ""), spec.dims)
+        # --eval_components: the policy (keep_largest, min_size) of the per-case scores (None = off)
+        self.components = _policy(cfg)
+        self._pp = None                       # (probabilities, threshold, filtered map, info) last filtered
 
     def set_buckets(self, bounds):
         self.bounds = list(bounds)
+
+    def _filter(self, p, threshold: float):
+        """(p, None) with the filter off, else (filtered p, info) of `ops.components`; the last
+        result is kept, so the stats, surface and info of one batch filter once, and a map
+        that is itself the last result (``predict_sliding``'s) is not filtered again."""
+        if self.components is None:
+            return p, None
+        c = self._pp
+        if c is not None and c[1] == threshold and (c[0] is p or c[2] is p):
+            return c[2], c[3]
+        out, info = cc.components_torch(p, threshold, *self.components)
+        self._pp = (p, threshold, out, info)
+        return out, info
 
     def _forward_logits(self, params, x, train, seed, dropout):
         with torch.autocast(self.device.type, dtype=self.dtype, enabled=self.dtype != torch.float32):
@@ -102,7 +126,7 @@ class TorchBackend:
         t = y.to(self.device).float()
         if self.tta:
             # the mean probability has no logits: BCE from the probabilities (log clamped at -100)
-            p = self.predict(x)
+            p = self._predict_raw(x)
             self._last_eval = (t, p)
             i, st, sp = losses.dice_sums(t, p)
             return torch.stack([i, st, sp, torch.nn.functional.binary_cross_entropy(p, t, reduction="sum")])
@@ -117,51 +141,77 @@ class TorchBackend:
     def last_eval_stats(self, threshold: float = 0.5) -> torch.Tensor:
         """[n][K][6] of the batch the last ``eval_sums`` scored."""
         t, p = self._last_eval
-        return seg_metrics.case_stats_torch(p, t, threshold)
+        return seg_metrics.case_stats_torch(self._filter(p, threshold)[0], t, threshold)
 
     @torch.no_grad()
     def eval_stats(self, x, y, threshold: float = 0.5) -> torch.Tensor:
         """[n][K][6] = {I, St, Sp, TP, FP, FN} per (sample, class) of the n samples given."""
-        return seg_metrics.case_stats_torch(self.predict(x), y.to(self.device).float(), threshold)
+        p = self._filter(self._predict_raw(x), threshold)[0]
+        return seg_metrics.case_stats_torch(p, y.to(self.device).float(), threshold)
 
     @torch.no_grad()
     def last_eval_surface(self, threshold: float = 0.5) -> torch.Tensor:
         """[n][K][4] = {mp, mt, q_lo, q_hi} of the batch the last ``eval_sums`` scored."""
         t, p = self._last_eval
-        return seg_metrics.case_surface_torch(p, t, threshold)
+        return seg_metrics.case_surface_torch(self._filter(p, threshold)[0], t, threshold)
 
     @torch.no_grad()
     def eval_surface(self, x, y, threshold: float = 0.5) -> torch.Tensor:
         """[n][K][4] = {mp, mt, q_lo, q_hi} per (sample, class) of the n samples given."""
-        return seg_metrics.case_surface_torch(self.predict(x), y.to(self.device).float(), threshold)
+        p = self._filter(self._predict_raw(x), threshold)[0]
+        return seg_metrics.case_surface_torch(p, y.to(self.device).float(), threshold)
+
+    @torch.no_grad()
+    def last_eval_components(self, threshold: float = 0.5) -> torch.Tensor:
+        """int32 [n][K][4] = {components, kept components, largest size, kept voxels} of the
+        batch the last ``eval_sums`` scored (--eval_components)."""
+        _need_policy(self)
+        return self._filter(self._last_eval[1], threshold)[1]
+
+    @torch.no_grad()
+    def eval_components(self, x, y=None, threshold: float = 0.5) -> torch.Tensor:
+        """int32 [n][K][4] per (sample, class) of the n samples given (y is not used)."""
+        _need_policy(self)
+        return self._filter(self._predict_raw(x), threshold)[1]
 
     def _predict1(self, x) -> torch.Tensor:
         logits = self._forward_logits(self.flat.params(), x, False, 0, self.cfg.eval_dropout).float()
         return torch.sigmoid(logits)
 
-    @torch.no_grad()
-    def predict(self, x) -> torch.Tensor:
-        """Probabilities of x; with --eval_tta their mean over the transforms (`tta_mean_torch`)."""
+    def _predict_raw(self, x) -> torch.Tensor:
         if self.tta:
             return tta_mean_torch(self._predict1, x.to(self.device), self.tta)
         return self._predict1(x)
+
+    @torch.no_grad()
+    def predict(self, x) -> torch.Tensor:
+        """Probabilities of x; with --eval_tta their mean over the transforms (`tta_mean_torch`);
+        with --eval_components filtered at --eval_threshold."""
+        return self._filter(self._predict_raw(x), getattr(self.cfg, "eval_threshold", 0.5))[0]
 
     @torch.no_grad()
     def predict_sliding(self, x, overlap: float = 0.5, blend: str = "gaussian") -> torch.Tensor:
         """Probabilities fp32 [n, (D,) H, W, K] of images of any spatial size: `predict` on
         overlapping tiles of the model's size, blended (`ops.sliding.sliding_predict_torch`)."""
         T = sliding.tile_shape(self.cfg.img_size, self.spec.dims)
-        return sliding.sliding_predict_torch(self.predict, x.to(self.device), T, self.B, overlap, blend)
+        p = sliding.sliding_predict_torch(self._predict_raw, x.to(self.device), T, self.B, overlap, blend)
+        return self._filter(p, getattr(self.cfg, "eval_threshold", 0.5))[0]
+
+    @torch.no_grad()
+    def sliding_components(self, p, threshold: float = 0.5) -> torch.Tensor:
+        """int32 [n][K][4] of full-size probabilities p (`predict_sliding`'s result)."""
+        _need_policy(self)
+        return self._filter(p, threshold)[1]
 
     @torch.no_grad()
     def sliding_stats(self, p, y, threshold: float = 0.5) -> torch.Tensor:
         """[n][K][6] of full-size probabilities p (`predict_sliding`) against the target y."""
-        return seg_metrics.case_stats_torch(p, y.to(p.device).float(), threshold)
+        return seg_metrics.case_stats_torch(self._filter(p, threshold)[0], y.to(p.device).float(), threshold)
 
     @torch.no_grad()
     def sliding_surface(self, p, y, threshold: float = 0.5) -> torch.Tensor:
         """[n][K][4] of full-size probabilities p (`predict_sliding`) against the target y."""
-        return seg_metrics.case_surface_torch(p, y.to(p.device).float(), threshold)
+        return seg_metrics.case_surface_torch(self._filter(p, threshold)[0], y.to(p.device).float(), threshold)
 
     def after_optimizer(self):
         pass
@@ -178,17 +228,22 @@ class NativeBackend:
         self.spec = spec
         # --eval_tta: the transform codes every evaluation forward is averaged over (() = off)
         self.tta = tta_codes(getattr(cfg, "eval_tta", ""), spec.dims)
+        # --eval_components: the policy (keep_largest, min_size) of the per-case scores (None = off)
+        self.components = _policy(cfg)
+        self._pp_thr = None                   # threshold at which prob_pp is the filter of the executor's prob
+        self._sw_pp = None                    # (probabilities, threshold, filtered map, info) of a full-size map
         if cfg.dtype == "fp32":
             # the reference's precision (test_dist.py:196-202): fp32 storage, fp32 MFMA
             self.engine = NativeUNetF32(spec, flat, per_rank_batch, cfg.img_size, device, loss=cfg.loss,
                                         bce_weight=cfg.bce_weight, bucket_bounds=bounds,
                                         eval_dropout=cfg.eval_dropout, eval_hd95=getattr(cfg, "eval_hd95", False),
-                                        eval_tta=bool(self.tta))
+                                        eval_tta=bool(self.tta), eval_components=self.components is not None)
         else:
             self.engine = NativeUNet(spec, flat, per_rank_batch, cfg.img_size, device, loss=cfg.loss,
                                      bce_weight=cfg.bce_weight, bucket_bounds=bounds,
                                      eval_dropout=cfg.eval_dropout, dtype=cfg.dtype,
-                                     eval_hd95=getattr(cfg, "eval_hd95", False), eval_tta=bool(self.tta))
+                                     eval_hd95=getattr(cfg, "eval_hd95", False), eval_tta=bool(self.tta),
+                                     eval_components=self.components is not None)
         self.B = per_rank_batch
         if getattr(cfg, "hip_graph", False):
             self.engine.enable_graphs()
@@ -200,6 +255,7 @@ class NativeBackend:
     def fwd_bwd(self, x, y, seed: int, on_segment=None, grad_scale: float = 1.0):
         """x, y: batch tensors, or x = a data.loader.ResidentBatch (y unused)."""
         e = self.engine
+        self._pp_thr = None
         e.set_loss_scale(grad_scale)
         if hasattr(x, "x_all"):
             if getattr(x, "aug", None) is not None:
@@ -236,17 +292,29 @@ class NativeBackend:
         """One evaluation of the full batch (x, y): the plain forward, or with --eval_tta the
         executor's `evaluate_tta` (the mean over the transforms; `sums` are then the mean's)."""
         e = self.engine
+        self._pp_thr = None
         if self.tta:
             e.evaluate_tta(x, y, self.tta)
         else:
             e.load_batch(x, y)
             e.evaluate_batch()
 
+    def _post(self, threshold: float) -> bool:
+        """With --eval_components: make `prob_pp` the filter of the executor's probabilities at
+        `threshold` (one `components` op per forward and threshold).  Returns whether the
+        per-case ops score `prob_pp`."""
+        if self.components is None:
+            return False
+        if self._pp_thr != threshold:
+            self.engine.components(threshold, *self.components)
+            self._pp_thr = threshold
+        return True
+
     @torch.no_grad()
     def last_eval_stats(self, threshold: float = 0.5) -> torch.Tensor:
         """[B][K][6] of the batch the last ``eval_sums`` scored: one more launch on the
         probabilities and target the executor still holds."""
-        return self.engine.case_stats(threshold).clone()
+        return self.engine.case_stats(threshold, post=self._post(threshold)).clone()
 
     @torch.no_grad()
     def eval_stats(self, x, y, threshold: float = 0.5) -> torch.Tensor:
@@ -255,7 +323,7 @@ class NativeBackend:
         moving BatchNorm statistics or per sample (GroupNorm), so the padding cannot change
         a real sample's result."""
         n = self._eval_padded(x, y, "eval_stats")
-        return self.engine.case_stats(threshold)[:n].clone()
+        return self.engine.case_stats(threshold, post=self._post(threshold))[:n].clone()
 
     def _eval_padded(self, x, y, what: str) -> int:
         """Evaluation forward of n <= B samples zero-padded to the per-rank batch; returns n."""
@@ -274,19 +342,40 @@ class NativeBackend:
     def last_eval_surface(self, threshold: float = 0.5) -> torch.Tensor:
         """int32 [B][K][4] = {mp, mt, q_lo, q_hi} of the batch the last ``eval_sums`` scored
         (surf_dist.h on the probabilities and target the executor still holds)."""
-        return self.engine.case_surface(threshold).clone()
+        return self.engine.case_surface(threshold, post=self._post(threshold)).clone()
 
     @torch.no_grad()
     def eval_surface(self, x, y, threshold: float = 0.5) -> torch.Tensor:
         """int32 [n][K][4] per (sample, class) of the n <= B samples given; a short batch is
         zero-padded like ``eval_stats``."""
         n = self._eval_padded(x, y, "eval_surface")
-        return self.engine.case_surface(threshold)[:n].clone()
+        return self.engine.case_surface(threshold, post=self._post(threshold))[:n].clone()
+
+    @torch.no_grad()
+    def last_eval_components(self, threshold: float = 0.5) -> torch.Tensor:
+        """int32 [B][K][4] = {components, kept components, largest size, kept voxels} of the
+        batch the last ``eval_sums`` scored (--eval_components; components.h)."""
+        _need_policy(self)
+        self._post(threshold)
+        return self.engine.components_info.clone()
+
+    @torch.no_grad()
+    def eval_components(self, x, y=None, threshold: float = 0.5) -> torch.Tensor:
+        """int32 [n][K][4] per (sample, class) of the n <= B samples given (y is not used); a
+        short batch is zero-padded like ``eval_stats``."""
+        _need_policy(self)
+        if y is None:
+            y = torch.zeros(x.shape[:-1] + (self.spec.n_cl_out,), device=x.device)
+        n = self._eval_padded(x, y, "eval_components")
+        self._post(threshold)
+        return self.engine.components_info[:n].clone()
 
     @torch.no_grad()
     def predict(self, x) -> torch.Tensor:
         e = self.engine
         self._evaluate(x, torch.zeros(x.shape[:-1] + (self.spec.n_cl_out,), device=x.device))
+        if self._post(getattr(self.cfg, "eval_threshold", 0.5)):       # --eval_components: the filtered map
+            return e.probs_pp().clone()
         return e.probs().clone()
 
     @torch.no_grad()
@@ -295,22 +384,55 @@ class NativeBackend:
         executor's sliding-window path (`native_engine.run_predict_sliding`: sw_extract, the
         evaluation forward -- with --eval_tta the mean over the transforms -- and sw_blend per
         batch of tiles, then sw_finish).  The executor's buffer, overwritten by the next call."""
-        return self.engine.predict_sliding(x.to(self.engine.device), overlap, blend, self.tta)
+        self._pp_thr = None                   # (the tiles' forwards overwrite the executor's prob)
+        p = self.engine.predict_sliding(x.to(self.engine.device), overlap, blend, self.tta)
+        return self._sw_filter(p, getattr(self.cfg, "eval_threshold", 0.5))[0]
+
+    def _sw_filter(self, p, threshold: float):
+        """(p, None) with the filter off, else (filtered p, info) of a full-size map
+        (`native_engine.sliding_components`); the last result is kept and a map that is itself
+        that result is not filtered again."""
+        if self.components is None:
+            return p, None
+        c = self._sw_pp
+        if c is not None and c[1] == threshold and c[2] is p:
+            return c[2], c[3]
+        from .native_engine import sliding_components
+        out, info = sliding_components(self.engine, p, threshold, *self.components)
+        self._sw_pp = (None, threshold, out, info)
+        return out, info
+
+    @torch.no_grad()
+    def sliding_components(self, p, threshold: float = 0.5) -> torch.Tensor:
+        """int32 [n][K][4] of full-size probabilities p (`predict_sliding`'s result)."""
+        _need_policy(self)
+        return self._sw_filter(p, threshold)[1]
 
     @torch.no_grad()
     def sliding_stats(self, p, y, threshold: float = 0.5) -> torch.Tensor:
         """fp32 [n][K][6] of full-size probabilities p (`predict_sliding`) against the target y."""
         from .native_engine import sliding_stats
-        return sliding_stats(self.engine, p, y, threshold)
+        return sliding_stats(self.engine, self._sw_filter(p, threshold)[0], y, threshold)
 
     @torch.no_grad()
     def sliding_surface(self, p, y, threshold: float = 0.5) -> torch.Tensor:
         """int32 [n][K][4] of full-size probabilities p (`predict_sliding`) against the target y."""
         from .native_engine import sliding_surface
-        return sliding_surface(self.engine, p, y, threshold)
+        return sliding_surface(self.engine, self._sw_filter(p, threshold)[0], y, threshold)
 
     def adam_step(self, lr, b1p, b2p, grad_scale=1.0):
         self.engine.adam_step(lr, b1p, b2p, grad_scale)
+
+
+def _policy(cfg):
+    """(keep_largest, min_size) of cfg.eval_components, or None with the flag off."""
+    s = str(getattr(cfg, "eval_components", "") or "")
+    return parse_components(s) if s.strip() else None
+
+
+def _need_policy(backend) -> None:
+    if backend.components is None:
+        raise RuntimeError("no component policy: build the backend with --eval_components (largest, min:V)")
 
 
 def _summary_arrays(x, t, p, n) -> dict:

@@ -34,8 +34,8 @@ import torch
 
 from .. import native
 from ..models.spec import UNetSpec
-from .native_engine import (gather_aug_args, plan_case_stats, plan_case_surface, plan_tta, run_case_stats,
-                            run_case_surface, run_evaluate_tta, run_predict_sliding)
+from .native_engine import (gather_aug_args, plan_case_stats, plan_case_surface, plan_components, plan_tta,
+                            run_case_stats, run_case_surface, run_components, run_evaluate_tta, run_predict_sliding)
 from .params import FlatParams
 from .plan_check import RecordingPlan
 
@@ -52,7 +52,7 @@ class NativeUNetF32:
     def __init__(self, spec: UNetSpec, flat: FlatParams, batch: int, img: int, device, loss: str = "dice",
                  bce_weight: float = 1.0, bucket_bounds: Optional[Sequence[int]] = None,
                  eval_dropout: bool = False, dry_run: bool = False, eval_hd95: bool = False,
-                 eval_tta: bool = False):
+                 eval_tta: bool = False, eval_components: bool = False):
         self.C = native.require()
         if spec.norm != "none":
             raise NotImplementedError("fp32 native executor: norm=%s (the reference has no normalisation; "
@@ -91,6 +91,9 @@ class NativeUNetF32:
         if eval_tta:             # (otherwise on the first evaluate_tta call)
             plan_tta(self, "f32_tta_finish")
         self.sw_plan = None      # (sliding-window inference: on the first predict_sliding call, or plan_sliding)
+        self.components_plan = self.prob_pp = self.components_info = self.components_scratch = None
+        if eval_components:      # (otherwise on the first components call)
+            plan_components(self)
         self._adam_segs()
 
     # ------------------------------------------------------------------ shapes / buffers
@@ -435,15 +438,28 @@ class NativeUNetF32:
         shape = (self.B, h, w, 1) if self.dims == 2 else (self.B, d, h, w, 1)
         return self.prob.view(shape)
 
-    def case_stats(self, threshold: float = 0.5, stream=None) -> torch.Tensor:
+    def case_stats(self, threshold: float = 0.5, stream=None, post: bool = False) -> torch.Tensor:
         """[B][1][6] = {I, St, Sp, TP, FP, FN} per sample of the probabilities and the fp32
-        target the last forward / evaluate_batch left behind (one launch, seg_stats.h)."""
-        return run_case_stats(self, "f32_seg_stats", threshold, stream)
+        target the last forward / evaluate_batch left behind (one launch, seg_stats.h);
+        `post`: of the filtered probabilities `prob_pp` of the last `components` call."""
+        return run_case_stats(self, "f32_seg_stats", threshold, stream, post)
 
-    def case_surface(self, threshold: float = 0.5, stream=None) -> torch.Tensor:
+    def case_surface(self, threshold: float = 0.5, stream=None, post: bool = False) -> torch.Tensor:
         """int32 [B][1][4] = {mp, mt, q_lo, q_hi} per sample of the probabilities and the fp32
-        target the last forward / evaluate_batch left behind (surf_dist.h)."""
-        return run_case_surface(self, "f32_surf_dist", threshold, stream)
+        target the last forward / evaluate_batch left behind (surf_dist.h); `post`: of the
+        filtered probabilities `prob_pp` of the last `components` call."""
+        return run_case_surface(self, "f32_surf_dist", threshold, stream, post)
+
+    def components(self, threshold: float = 0.5, keep_largest: bool = True, min_size: int = 0,
+                   stream=None) -> torch.Tensor:
+        """Connected-component filter (components.h) of the probabilities the last forward /
+        evaluate_batch left behind: `prob_pp` holds the filtered map; returns the int32
+        [B][1][4] = {components, kept components, largest size, kept voxels} buffer."""
+        return run_components(self, threshold, keep_largest, min_size, stream)
+
+    def probs_pp(self) -> torch.Tensor:
+        """`prob_pp` in the shape of `probs()` (after a `components` call)."""
+        return self.prob_pp.view(self.probs().shape)
 
     def evaluate_tta(self, x: torch.Tensor, y: torch.Tensor, codes, stream=None):
         """Test-time augmentation of the batch (x, y) over the transform codes `codes`

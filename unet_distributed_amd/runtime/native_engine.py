@@ -218,7 +218,7 @@ class NativeUNet:
                  device, loss: str = "dice", bce_weight: float = 1.0,
                  bucket_bounds: Optional[Sequence[int]] = None, eval_dropout: bool = False,
                  dry_run: bool = False, dtype: str = "bf16", opts: Optional[Dict[str, int]] = None,
-                 eval_hd95: bool = False, eval_tta: bool = False):
+                 eval_hd95: bool = False, eval_tta: bool = False, eval_components: bool = False):
         self.C = native.require()
         self.opts = engine_options(opts)
         if spec.norm not in ("none", "batch", "group"):
@@ -302,6 +302,9 @@ class NativeUNet:
         if eval_tta:             # (otherwise on the first evaluate_tta call)
             plan_tta(self, "tta_finish")
         self.sw_plan = None      # (sliding-window inference: on the first predict_sliding call, or plan_sliding)
+        self.components_plan = self.prob_pp = self.components_info = self.components_scratch = None
+        if eval_components:      # (otherwise on the first components call)
+            plan_components(self)
         if not dry_run:          # dry_run: plan construction only (CPU tests, no GPU launches)
             self.repack()
 
@@ -2166,19 +2169,33 @@ class NativeUNet:
         shape = (self.B, h, w, self.K) if self.dims == 2 else (self.B, d, h, w, self.K)
         return self.prob.view(shape)
 
-    def case_stats(self, threshold: float = 0.5, stream=None) -> torch.Tensor:
+    def case_stats(self, threshold: float = 0.5, stream=None, post: bool = False) -> torch.Tensor:
         """[B][K][6] = {I, St, Sp, TP, FP, FN} per (sample, class) of the probabilities and
         target the last forward / evaluate_batch left behind (one launch; the returned
-        tensor is the executor's buffer, overwritten by the next call)."""
-        return run_case_stats(self, "seg_stats", threshold, stream)
+        tensor is the executor's buffer, overwritten by the next call).  `post`: of the
+        filtered probabilities `prob_pp` the last `components` call left behind."""
+        return run_case_stats(self, "seg_stats", threshold, stream, post)
 
-    def case_surface(self, threshold: float = 0.5, stream=None) -> torch.Tensor:
+    def case_surface(self, threshold: float = 0.5, stream=None, post: bool = False) -> torch.Tensor:
         """int32 [B][K][4] = {mp, mt, q_lo, q_hi} per (sample, class): the surface sizes of
         {prob >= threshold} and {target >= 0.5} and the two squared surface distances that
         bracket the 95th percentile (`ops.seg_metrics.hd95_from_surface`), of the
         probabilities and target the last forward / evaluate_batch left behind.  The
-        returned tensor is the executor's buffer, overwritten by the next call."""
-        return run_case_surface(self, "surf_dist", threshold, stream)
+        returned tensor is the executor's buffer, overwritten by the next call.  `post`: of
+        the filtered probabilities `prob_pp` the last `components` call left behind."""
+        return run_case_surface(self, "surf_dist", threshold, stream, post)
+
+    def components(self, threshold: float = 0.5, keep_largest: bool = True, min_size: int = 0,
+                   stream=None) -> torch.Tensor:
+        """Connected-component filter (kernels/components.h, `ops.components` is the
+        definition) of the probabilities the last forward / evaluate_batch left behind:
+        `prob_pp` (see `probs_pp`) holds the filtered map and the returned int32 [B][K][4] =
+        {components, kept components, largest size, kept voxels} is the executor's buffer."""
+        return run_components(self, threshold, keep_largest, min_size, stream)
+
+    def probs_pp(self) -> torch.Tensor:
+        """`prob_pp` in the shape of `probs()` (after a `components` call)."""
+        return self.prob_pp.view(self.probs().shape)
 
     def evaluate_tta(self, x: torch.Tensor, y: torch.Tensor, codes, stream=None):
         """Test-time augmentation of the batch (x, y) over the transform codes `codes`
@@ -2233,12 +2250,12 @@ def plan_case_stats(e, kind: str) -> None:
     e.stats_plan.add_generic(kind, e._case_stats_args[0], e._case_stats_args[1], [0.5], "case_stats")
 
 
-def run_case_stats(e, kind: str, threshold: float, stream) -> torch.Tensor:
+def run_case_stats(e, kind: str, threshold: float, stream, post: bool = False) -> torch.Tensor:
     if e._case_stats_err is not None:
         raise ValueError(e._case_stats_err)
     if e._dry:
         raise RuntimeError("executor built with dry_run=True: case_stats is validated, not launched")
-    ptrs, ints = e._case_stats_args
+    ptrs, ints = _post_args(e, e._case_stats_args) if post else e._case_stats_args
     e.C.generic(kind, ptrs, ints, [float(threshold)], native.stream_handle(stream), getattr(e, "dt_id", 0))
     return e.case_stats_buf
 
@@ -2306,14 +2323,14 @@ def plan_case_surface(e, kind: str) -> None:
     e.surface_plan.add_generic(kind, e._case_surface_args[0], [group, d, h, w, K], [0.5], "case_surface")
 
 
-def run_case_surface(e, kind: str, threshold: float, stream) -> torch.Tensor:
+def run_case_surface(e, kind: str, threshold: float, stream, post: bool = False) -> torch.Tensor:
     if e._dry:
         raise RuntimeError("executor built with dry_run=True: case_surface is validated, not launched")
     if e.surface_plan is None and getattr(e, "_case_surface_err", None) is None:
         plan_case_surface(e, kind)
     if e._case_surface_err is not None:
         raise ValueError(e._case_surface_err)
-    ptrs, ints = e._case_surface_args
+    ptrs, ints = _post_args(e, e._case_surface_args) if post else e._case_surface_args
     launch_surf_dist(e.C, kind, ptrs, ints, threshold, e.case_surface_scratch.numel() * 4,
                      e.target.element_size(), native.stream_handle(stream), getattr(e, "dt_id", 0))
     return e.case_surface_buf
@@ -2503,3 +2520,122 @@ def sliding_surface(e, prob: torch.Tensor, y: torch.Tensor, threshold: float = 0
     launch_surf_dist(e.C, "f32_surf_dist", [_ptr(prob), _ptr(y), _ptr(out), _ptr(scratch)], [N, d, h, w, K],
                      threshold, scratch.numel() * 4, 4, native.stream_handle(stream), 0)
     return out
+
+
+# cap of an executor's components scratch: 8 bytes per (voxel, class) of a sample group (the
+# int32 label and size planes), as surf_dist's fields: the same 256 MiB, the same groups
+COMP_SCRATCH_CAP = SURF_SCRATCH_CAP
+
+
+def components_group(C, N: int, D: int, H: int, W: int, K: int, cap: int = COMP_SCRATCH_CAP) -> int:
+    """Samples per `components` launch under the byte cap `cap` (at least one sample): the
+    fewest groups that fit, of equal size but for the last.  ValueError with the op's reason
+    where it refuses the shape."""
+    C.components_scratch(1, D, H, W, K)                   # (the op's refusal of the shape, if any)
+    lo, hi = 1, N                                         # the most samples whose scratch fits the cap
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if C.components_scratch(mid, D, H, W, K) <= cap:
+            lo = mid
+        else:
+            hi = mid - 1
+    groups = -(-N // lo)
+    return -(-N // groups)
+
+
+def launch_components(C, ptrs, ints, threshold: float, keep_largest: bool, min_size: int, group: int,
+                      stream=0) -> int:
+    """Issue `components` (bindings.cpp) over N samples as immediate ops on groups of `group`
+    consecutive samples.  ptrs = [prob, out, info, scratch], ints = [N, D, H, W, K]; prob, out
+    and info are sample-major, so a group is a pointer offset; the scratch holds
+    components_scratch(group, ...) bytes.  Returns the number of launches (6 kernels each)."""
+    N, D, H, W, K = ints
+    S = D * H * W
+    prob, out, info, scratch = ptrs
+    n0 = launches = 0
+    while n0 < N:
+        n = min(group, N - n0)
+        C.generic("components", [prob + n0 * S * K * 4, out + n0 * S * K * 4, info + n0 * K * 16, scratch],
+                  [n, D, H, W, K, int(bool(keep_largest)), int(min_size)], [float(threshold)], stream, 0)
+        n0 += n
+        launches += 1
+    return launches
+
+
+def plan_components(e) -> None:
+    """Buffers and the validation plan of an executor's `components` (kernels/components.h):
+    `prob_pp` (the size of `prob`), the int32 [B][K][4] `components_info` and the scratch of
+    one sample group under COMP_SCRATCH_CAP.  Also the second argument sets of `case_stats`
+    / `case_surface`, which score `prob_pp` in place of `prob`.
+
+    Like `case_stats` the op is in neither `plan` nor `eval_plan`: `components_plan` holds the
+    op of the first sample group alone (threshold 0.5, keep the largest) for the static plan
+    validation."""
+    K = getattr(e, "K", 1)
+    d, h, w = e.sdims(1)
+    e.components_plan = e.prob_pp = e.components_info = e.components_scratch = None
+    try:
+        group = components_group(e.C, e.B, d, h, w, K)
+        need = e.C.components_scratch(group, d, h, w, K)
+    except ValueError as err:
+        e._components_err = str(err)
+        return
+    e._components_err = None
+    e._components_group = group
+    e.prob_pp = torch.zeros_like(e.prob)
+    e.components_info = torch.zeros(e.B, K, 4, dtype=torch.int32, device=e.device)
+    e.components_scratch = torch.empty(need // 4, dtype=torch.int32, device=e.device)
+    e._components_args = ([_ptr(e.prob), _ptr(e.prob_pp), _ptr(e.components_info), _ptr(e.components_scratch)],
+                          [e.B, d, h, w, K])
+    e.components_plan = RecordingPlan(e.C.Plan(getattr(e, "dt_id", 0)))
+    e.components_plan.add_generic("components", e._components_args[0], [group, d, h, w, K, 1, 0], [0.5],
+                                  "components")
+
+
+def _post_args(e, args):
+    """The argument set (ptrs, ints) of `case_stats` / `case_surface` with `prob_pp` for `prob`."""
+    if getattr(e, "prob_pp", None) is None:
+        raise RuntimeError("no filtered probabilities: call components() before scoring prob_pp")
+    ptrs, ints = args
+    return [_ptr(e.prob_pp)] + list(ptrs[1:]), ints
+
+
+def run_components(e, threshold: float, keep_largest: bool, min_size: int, stream) -> torch.Tensor:
+    if e._dry:
+        raise RuntimeError("executor built with dry_run=True: components is validated, not launched")
+    if not 0.0 < float(threshold) < 1.0:
+        raise ValueError("components: threshold strictly inside (0, 1)")
+    if int(min_size) < 0:
+        raise ValueError("components: min_size >= 0")
+    if e.components_plan is None and getattr(e, "_components_err", None) is None:
+        plan_components(e)
+    if e._components_err is not None:
+        raise ValueError(e._components_err)
+    ptrs, ints = e._components_args
+    launch_components(e.C, ptrs, ints, threshold, keep_largest, min_size, e._components_group,
+                      native.stream_handle(stream))
+    return e.components_info
+
+
+def sliding_components(e, prob: torch.Tensor, threshold: float = 0.5, keep_largest: bool = True, min_size: int = 0,
+                       stream=None, cap: int = COMP_SCRATCH_CAP):
+    """(out fp32 like prob, info int32 [N][K][4]) of full-size probabilities prob [N, (D,) H, W, K]
+    (`run_predict_sliding`'s result): the `components` op at the images' own size in groups
+    that fit `cap`, or `components_torch` on the device where the op refuses the shape."""
+    from ..ops import components as cc
+    prob = prob.contiguous()
+    N, K = prob.shape[0], prob.shape[-1]
+    d, h, w = tuple(prob.shape[1:4]) if prob.dim() == 5 else (1,) + tuple(prob.shape[1:3])
+    try:
+        if e.C.components_check(N, d, h, w, K, int(min_size)) is not None:
+            raise ValueError
+        group = components_group(e.C, N, d, h, w, K, cap)
+    except ValueError:
+        out, info = cc.components_torch(prob, threshold, keep_largest, min_size)
+        return out, info
+    out = torch.empty_like(prob)
+    info = torch.zeros(N, K, 4, dtype=torch.int32, device=prob.device)
+    scratch = torch.empty(e.C.components_scratch(group, d, h, w, K) // 4, dtype=torch.int32, device=prob.device)
+    launch_components(e.C, [_ptr(prob), _ptr(out), _ptr(info), _ptr(scratch)], [N, d, h, w, K], threshold,
+                      keep_largest, min_size, group, native.stream_handle(stream))
+    return out, info

@@ -108,6 +108,10 @@ def _generic_write_spans(kind: str, p: List[int], ints: List[int]) -> List[Tuple
     if kind in ("surf_dist", "f32_surf_dist") and len(p) > 3 and len(ints) >= 5:
         N, D, H, W, K = ints[:5]
         return [(p[2], N * K * 4 * 4), (p[3], surf_dist_scratch(N, D, H, W, K))]
+    # component filter (N, D, H, W, K in ints): the filtered map, N K 4 ints of info and the scratch
+    if kind == "components" and len(p) > 3 and len(ints) >= 5:
+        N, D, H, W, K = ints[:5]
+        return [(p[1], N * D * H * W * K * 4), (p[2], N * K * 4 * 4), (p[3], components_scratch(N, D, H, W, K))]
     # augmenting batch gather (B, D, H, W, Cin, Cpad, K in ints): the padded input and the target,
     # 16-bit (gather_batch_aug) or fp32 (f32_gather_batch_aug)
     if kind in ("gather_batch_aug", "f32_gather_batch_aug") and len(p) > 6 and len(ints) >= 7:
@@ -154,6 +158,14 @@ def surf_dist_scratch(N: int, D: int, H: int, W: int, K: int) -> int:
     """Scratch bytes of a surf_dist launch over N samples: int32 fields [N][K][2][S]
     (mirrors csrc/kernels/surf_dist.hip)."""
     return N * K * 2 * D * H * W * 4
+
+
+def components_scratch(N: int, D: int, H: int, W: int, K: int) -> int:
+    """Scratch bytes of a components launch over N samples: int32 label and size planes
+    [N][K][S], sel [N][K] and the selection's parts [N][K][P][5], P = ceil(S / 16384), rounded up
+    to 16 (mirrors csrc/kernels/f32_components.hip)."""
+    S = D * H * W
+    return (N * K * (2 * S + 1 + 5 * (-(-S // 16384))) * 4 + 15) // 16 * 16
 
 
 def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], List[int]]:
@@ -209,6 +221,8 @@ def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], Li
         return _sel(p, [0, 1]), _sel(p, [2, 3])
     if kind in ("surf_dist", "f32_surf_dist"):
         return _sel(p, [0, 1]), _sel(p, [2, 3])
+    if kind == "components":
+        return _sel(p, [0]), _sel(p, [1, 2, 3])
     if kind in ("gather_batch_aug", "f32_gather_batch_aug"):
         return [q for q in _sel(p, [0, 1, 2, 3, 4]) if q], _sel(p, [5, 6])
     if kind == "tta_acc":                # (write mode reads no element of the accumulator)
@@ -340,7 +354,7 @@ def engine_regions(e) -> Tuple[_Regions, set]:
     for k in ("prob", "target", "sums", "head_partial", "head_ws", "slab", "bias_slab", "red_stage", "arena",
               "loss_scale_dev", "_no_dy", "case_stats_buf", "case_stats_partial",
               "case_surface_buf", "case_surface_scratch", "tta_acc_buf", "tta_partial",
-              "sw_src", "sw_x", "sw_w", "sw_acc", "sw_wsum"):
+              "sw_src", "sw_x", "sw_w", "sw_acc", "sw_wsum", "prob_pp", "components_info", "components_scratch"):
         R.add(k, getattr(e, k, None))
     inputs |= {"target", "arena", "loss_scale_dev", "_no_dy"}
     for k, t in getattr(e, "state", {}).items():
@@ -468,4 +482,27 @@ def check_surface_plan(e) -> List[str]:
     if have < need:
         errs.append("case_surface: case_surface_scratch holds %d bytes, a group of %d samples needs %d"
                     % (have, e._case_surface_group, need))
+    return errs
+
+
+def check_components_plan(e) -> List[str]:
+    """Errors of executor `e`'s `components` op (`components_plan`, built on first use or with
+    --eval_components): it reads the probabilities the forward / evaluation plan left behind
+    and writes `prob_pp`, `components_info` and the scratch.  The plan holds the op of the
+    first group of samples; `prob_pp` must be the size of `prob`, the info hold every group's
+    rows and the scratch one group."""
+    if getattr(e, "components_plan", None) is None:
+        return [getattr(e, "_components_err", None) or "components is not planned (plan_components)"]
+    errs = check_plan(e, e.components_plan, False, extra_inputs=("prob",))
+    K, (d, h, w) = getattr(e, "K", 1), e.sdims(1)
+    if e.prob_pp.numel() != e.prob.numel() or e.prob_pp.dtype != torch.float32:
+        errs.append("components: prob_pp holds %d floats, prob %d" % (e.prob_pp.numel(), e.prob.numel()))
+    if e.components_info.numel() < e.B * K * 4:
+        errs.append("components: components_info holds %d ints, B K 4 = %d needed"
+                    % (e.components_info.numel(), e.B * K * 4))
+    need = components_scratch(e._components_group, d, h, w, K)
+    have = e.components_scratch.numel() * e.components_scratch.element_size()
+    if have < need:
+        errs.append("components: components_scratch holds %d bytes, a group of %d samples needs %d"
+                    % (have, e._components_group, need))
     return errs

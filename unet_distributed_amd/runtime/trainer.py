@@ -229,6 +229,9 @@ class Trainer:
             if cfg.eval_tta:
                 print("Evaluation TTA: %s (%d passes)" % (", ".join(parse_tta(cfg.eval_tta)),
                                                           len(tta_codes(cfg.eval_tta, cfg.dims))))
+            if cfg.eval_components.strip():
+                from ..ops.components import describe
+                print("Evaluation components: %s" % describe(cfg.eval_components))
 
     def _batch(self, idx: np.ndarray, step: int = 0):
         # native backend + resident data: the backend gathers the batch itself (one
@@ -253,7 +256,11 @@ class Trainer:
         and `hd95` (voxels; `last_eval_surface` per full batch, `eval_surface` for the tail).
         With `--eval_tta` every one of these forwards is the backend's mean over the transforms
         (the loss term of the batch metrics is then the BCE of the mean probabilities) and the
-        dict carries `tta`, the number of passes."""
+        dict carries `tta`, the number of passes.  With `--eval_components` the per-class lines,
+        `case_dice` and HD95 are of the connected-component-filtered map (the per-class soft Dice
+        too; the pooled batch metrics are not), `per_class["components"]` /
+        `per_class["components_kept"]` are the mean per case of the component counts before and
+        after the filter and the dict carries `components`, the flag string."""
         n = len(self.x_test)
         B = self.per_rank
         nbatches = n // B
@@ -273,6 +280,12 @@ class Trainer:
         def surface(surf, y):
             hd[:] += seg_metrics.accumulate_hd95(surf, tuple(y.shape[1:-1]))["hd95_sum"]
 
+        cc = np.zeros(2 * K, dtype=np.float64)  # --eval_components: per-class sums of components | kept components
+        want_cc = bool(self.cfg.eval_components.strip())
+
+        def comps(info):
+            cc[:] += info[..., :2].double().sum(dim=0).t().reshape(-1).cpu().numpy()
+
         def load(lo, hi):
             return (torch.from_numpy(np.ascontiguousarray(self.x_test[lo:hi])).to(self.device),
                     torch.from_numpy(np.ascontiguousarray(self.y_test[lo:hi])).to(self.device))
@@ -287,13 +300,18 @@ class Trainer:
             hard(stats, y[0].numel() // K)
             if want_hd:
                 surface(self.backend.last_eval_surface(thr), y)
+            if want_cc:
+                comps(self.backend.last_eval_components(thr))
         if n % B and self.rank == nbatches % self.world:
             x, y = load(nbatches * B, n)
             hard(self.backend.eval_stats(x, y, thr), y[0].numel() // K)
             if want_hd:
                 surface(self.backend.eval_surface(x, y, thr), y)
+            if want_cc:
+                comps(self.backend.eval_components(x, y, thr))
         D.allreduce_sum_(acc)
-        cls_t = torch.from_numpy(np.concatenate([cls, hd]) if want_hd else cls).to(self.device)
+        extra = ([hd] if want_hd else []) + ([cc] if want_cc else [])
+        cls_t = torch.from_numpy(np.concatenate([cls] + extra) if extra else cls).to(self.device)
         D.allreduce_sum_(cls_t)                 # (every rank, whether or not it owns the tail)
         cls = cls_t.cpu().numpy()
         cnt = max(acc[4].item(), 1.0)
@@ -309,6 +327,12 @@ class Trainer:
             hm95 = seg_metrics.hd95_metrics({"hd95_sum": cls[6 * K + 1:7 * K + 1], "cases": cls[6 * K]})
             m["per_class"]["hd95"] = hm95["hd95"]
             m["hd95"] = hm95["hd95_mean"]
+        if want_cc:
+            o = 6 * K + 1 + (K if want_hd else 0)
+            cases = max(cls[6 * K], 1.0)
+            m["per_class"]["components"] = [float(v) / cases for v in cls[o:o + K]]
+            m["per_class"]["components_kept"] = [float(v) / cases for v in cls[o + K:o + 2 * K]]
+            m["components"] = self.cfg.eval_components
         if self.cfg.eval_tta:                   # every forward above was the mean over this many passes
             m["tta"] = len(tta_codes(self.cfg.eval_tta, self.cfg.dims))
         return m

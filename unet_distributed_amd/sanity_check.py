@@ -47,6 +47,9 @@ def main(argv=None) -> float:
                    help="also print the per-class 95th-percentile Hausdorff distance in voxels (thresholded at 0.5)")
     p.add_argument("--tta", default="", metavar="SPEC",
                    help="test-time augmentation: score the mean prediction over flip and / or rot90 (comma-separated)")
+    p.add_argument("--components", default="", metavar="SPEC",
+                   help="connected-component filter of the thresholded prediction before scoring: a comma list of "
+                        "largest and / or min:V (voxels), e.g. largest,min:20")
     p.add_argument("--synthetic", type=int, default=0, metavar="N",
                    help="use N synthetic test slices instead of the .npy files")
     p.add_argument("--synthetic_size", type=int, default=0, metavar="S",
@@ -64,7 +67,11 @@ def main(argv=None) -> float:
         p.error("--overlap must lie in [0, 0.75], got %r" % a.overlap)
     from .inference import load_saved_model
     print("Loading trained model from directory {}".format(a.export_dir))
-    model = load_saved_model(a.export_dir, device=a.device, batch=a.batch_size, backend=a.backend, tta=a.tta)
+    model = load_saved_model(a.export_dir, device=a.device, batch=a.batch_size, backend=a.backend, tta=a.tta,
+                             components=a.components)
+    if a.components.strip():
+        from .ops.components import describe
+        print("Evaluation components: %s" % describe(a.components))
     print('-' * 38)
     print('Loading and preprocessing test data...')
     print('-' * 38)
@@ -84,6 +91,7 @@ def main(argv=None) -> float:
     predict = (lambda v: model.predict_sliding(v, **sw)) if a.sliding else model.predict
     stats_of = (lambda v, t: model.stats_sliding(v, t, **sw)) if a.sliding else model.stats
     surface_of = (lambda v, t: model.surface_sliding(v, t, **sw)) if a.sliding else model.surface
+    comps_of = (lambda v: model.components_sliding(v, **sw)) if a.sliding else model.components
     dice, nb = 0.0, 0
     t0 = time.time()
     for s in batch_starts(len(x), a.batch_size, every):
@@ -103,10 +111,16 @@ def main(argv=None) -> float:
                           np.asarray(y[s:s + a.batch_size], dtype=np.float32))
                  for s in batch_starts(len(x), a.batch_size, every)]
         m = seg_metrics.metrics_from_case_stats(np.concatenate(stats), int(np.prod(y.shape[1:])) // K)
+        tails = [""] * K
+        if a.components.strip():              # mean components per case before -> after the filter
+            info = np.concatenate([comps_of(np.asarray(x[s:s + a.batch_size], dtype=np.float32))
+                                   for s in batch_starts(len(x), a.batch_size, every)]).astype(np.float64)
+            tails = [", components = {:.2f} -> {:.2f}".format(info[:, k, 0].mean(), info[:, k, 1].mean())
+                     for k in range(K)]
         for k in range(K):
-            print("class {}: case Dice = {}, sensitivity = {}, specificity = {}".format(
+            print("class {}: case Dice = {}, sensitivity = {}, specificity = {}{}".format(
                 k, seg_metrics.fmt(m["case_dice"][k]), seg_metrics.fmt(m["sensitivity"][k]),
-                seg_metrics.fmt(m["specificity"][k])))
+                seg_metrics.fmt(m["specificity"][k]), tails[k]))
         print("Case Dice = {} ({} cases)".format(seg_metrics.fmt(m["case_dice_mean"]), m["cases"]))
     if a.hd95 and nb:
         from .ops import seg_metrics

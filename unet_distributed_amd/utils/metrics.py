@@ -74,9 +74,12 @@ class MetricLogger:
         pc = m.get("per_class")
         if pc:
             for k in range(len(pc["dice"])):
-                print("class {}: Dice = {}, case Dice = {}, sensitivity = {}, specificity = {}".format(
+                # --eval_components: mean components per case before -> after the filter
+                tail = (", components = {:.2f} -> {:.2f}".format(pc["components"][k], pc["components_kept"][k])
+                        if "components" in pc else "")
+                print("class {}: Dice = {}, case Dice = {}, sensitivity = {}, specificity = {}{}".format(
                     k, fmt(pc["dice"][k]), fmt(pc["case_dice"][k]), fmt(pc["sensitivity"][k]),
-                    fmt(pc["specificity"][k])))
+                    fmt(pc["specificity"][k]), tail))
             print("Case Dice = {} ({} cases)".format(fmt(m["case_dice"]), m["cases"]), flush=True)
             if "hd95" in pc:                    # --eval_hd95: in voxels
                 for k in range(len(pc["hd95"])):
@@ -96,6 +99,10 @@ class MetricLogger:
                     tags["hd95_test"] = m["hd95"]
                     for k in range(len(pc["hd95"])):
                         tags["hd95_test/class_%d" % k] = pc["hd95"][k]
+                if "components" in pc:
+                    for k in range(len(pc["components"])):
+                        tags["components_test/class_%d" % k] = pc["components"][k]
+                        tags["components_kept_test/class_%d" % k] = pc["components_kept"][k]
                 self.events.scalars(step, tags)
             self.events.flush()
 
