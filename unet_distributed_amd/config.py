@@ -71,6 +71,7 @@ class Config:
     synthetic_train: int = 2048
     synthetic_test: int = 256
     synthetic_difficulty: str = "easy"   # easy | hard (datasets.synthetic_brats)
+    synthetic_size: int = 0          # stored side of the synthetic train / test images (0: img_size)
     data_on_device: str = "auto"     # auto | on | off: keep the train set resident in HBM
     data_path: str = settings.OUT_PATH
     steps: int = 0                   # >0 overrides epochs*num_batches
@@ -107,6 +108,9 @@ class Config:
     augment_intensity: float = 0.1   # intensity: scale in [1-a, 1+a], shift in [-a, a] per (sample, channel)
     eval_tta: str = ""               # evaluation only: mean prediction over flip and / or rot90 (comma-separated)
     eval_components: str = ""        # evaluation only: connected-component filter, comma list of largest, min:V
+    crop: str = ""                   # training patches of img_size from larger stored images: random | foreground[:P]
+    eval_overlap: float = 0.5        # sliding-window evaluation (test images not of the model's size): window overlap
+    eval_blend: str = "gaussian"     # ... and window weighting: constant | gaussian
 
     @property
     def method_up(self):
@@ -128,6 +132,7 @@ _CHOICES = {
     "dist_backend": ("auto", "nccl", "gloo"),
     "data_on_device": ("auto", "on", "off"),
     "synthetic_difficulty": ("easy", "hard"),
+    "eval_blend": ("constant", "gaussian"),
 }
 
 
@@ -186,6 +191,36 @@ def parse_components(s: str) -> tuple:
     return largest, min_size
 
 
+CROP_MODES = ("random", "foreground")
+CROP_P_FG = 1.0 / 3.0                # plain `foreground`: the share of patches forced to hold foreground
+
+
+def parse_crop(s: str) -> tuple:
+    """The --crop string as (mode, p_fg): "" is ("", 0.0), cropping off; `random` is
+    ("random", 0.0); `foreground` or `foreground:P` (P in (0, 1], default 1/3) is
+    ("foreground", P).  An unknown, malformed or repeated item is a SystemExit that names it."""
+    items = [t.strip() for t in str(s).split(",")] if str(s).strip() else []
+    if not items:
+        return "", 0.0
+    if len(items) > 1:
+        raise SystemExit("--crop: one mode, %r is listed after %r" % (items[1], items[0]))
+    t = items[0]
+    name, _, v = t.partition(":")
+    if name not in CROP_MODES or (":" in t and name != "foreground"):
+        raise SystemExit("--crop: unknown item %r (choose from random, foreground, foreground:P)" % t)
+    if name == "random":
+        return "random", 0.0
+    if ":" not in t:
+        return "foreground", CROP_P_FG
+    try:
+        p = float(v)
+    except ValueError:
+        p = float("nan")
+    if not 0.0 < p <= 1.0:
+        raise SystemExit("--crop: foreground:P takes a probability P in (0, 1], got %r" % t)
+    return "foreground", p
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(
         description="MI355X-native distributed UNet trainer "
@@ -234,6 +269,16 @@ def validate(cfg: Config) -> None:
     parse_augment(cfg.augment)
     parse_tta(cfg.eval_tta)
     parse_components(cfg.eval_components)
+    parse_crop(cfg.crop)
+    if cfg.synthetic_size < 0:
+        raise SystemExit("--synthetic_size must be >= 0 (0: --img_size)")
+    from .ops.sliding import check_overlap
+    try:
+        check_overlap(cfg.eval_overlap)
+    except ValueError as e:
+        raise SystemExit("--eval_overlap: %s" % e)
+    if cfg.eval_blend not in _CHOICES["eval_blend"]:
+        raise SystemExit("--eval_blend must be constant or gaussian")
     if not 0.0 <= cfg.augment_intensity < 1.0:
         raise SystemExit("--augment_intensity must be in [0, 1)")
     if cfg.mode == 5 and cfg.out_channels > 3:

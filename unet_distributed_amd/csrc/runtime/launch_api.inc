@@ -33,6 +33,14 @@ const char* gather_aug_check(long long B, long long D, long long H, long long W,
 hipError_t gather_batch_aug_launch(const float* x_all, const float* y_all, const long long* idx, const int* code,
                                    const float* affine, int B, int D, int H, int W, int Cin, int Cpad, int K, void* xb,
                                    void* tb, hipStream_t s);
+// gather_batch_aug reading a D x H x W patch at origin (int32 [B][3] = (d, h, w), clamped into
+// the sample by the kernel) of stored Ds x Hs x Ws samples (gather_crop.h); code may be null
+// (= 0); H == W, patch <= stored on every axis
+const char* gather_crop_check(long long B, long long Ds, long long Hs, long long Ws, long long D, long long H,
+                              long long W, long long Cin, long long Cpad, long long K);
+hipError_t gather_batch_crop_launch(const float* x_all, const float* y_all, const long long* idx, const int* origin,
+                                    const int* code, const float* affine, int B, int Ds, int Hs, int Ws, int D, int H,
+                                    int W, int Cin, int Cpad, int K, void* xb, void* tb, hipStream_t s);
 // code: optional uint32 per (pooled pixel, 8 channels) = first-argmax index per channel
 // (2 / 3 bits); the backward reads it instead of x when non-null
 hipError_t maxpool2_fwd_launch(const void* x, int N, int D, int H, int W, int C, int dims3, void* y, void* code,
@@ -213,6 +221,11 @@ hipError_t f32_seg_stats_launch(const float* prob, const float* t, int N, int S,
 hipError_t f32_gather_batch_aug_launch(const float* x_all, const float* y_all, const long long* idx, const int* code,
                                        const float* affine, int B, int D, int H, int W, int Cin, int Cpad, int K,
                                        float* xb, float* tb, hipStream_t s);
+// gather_batch_crop with fp32 outputs (f32_gather_crop.hip)
+hipError_t f32_gather_batch_crop_launch(const float* x_all, const float* y_all, const long long* idx,
+                                        const int* origin, const int* code, const float* affine, int B, int Ds, int Hs,
+                                        int Ws, int D, int H, int W, int Cin, int Cpad, int K, float* xb, float* tb,
+                                        hipStream_t s);
 // surf_dist with an fp32 target (f32_surf_dist.hip)
 hipError_t f32_surf_dist_launch(const float* prob, const float* t, int N, int D, int H, int W, int K, float thr,
                                 int* field, int* surf, hipStream_t s);

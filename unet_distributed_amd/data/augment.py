@@ -16,13 +16,18 @@ run repeats the run it resumes.  :func:`apply_torch` is the transform in plain t
 (the ATen backend, streamed data, and the oracle of the HIP kernel
 ``csrc/kernels/gather_aug.h``, which applies the same parameters inside the resident
 batch gather).
+
+``--crop`` adds a patch origin per sample: :func:`draw_crop` draws it from hash words of its
+own (the codes and affines above do not change), :func:`crop_torch` is the crop in plain
+torch, and the whole transform is ``apply_torch(*crop_torch(x, y, origin, patch), code,
+affine)`` -- the oracle of ``csrc/kernels/gather_crop.h``.
 """
 
 from typing import Callable, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..config import parse_augment, parse_tta
+from ..config import parse_augment, parse_crop, parse_tta
 
 FW, FH, T, FD = 1, 2, 4, 8
 # np.rot90(m, k) of the (H, W) plane for k = 0..3 as codes
@@ -39,13 +44,14 @@ def _mix(z: np.ndarray) -> np.ndarray:
     return z ^ (z >> np.uint64(31))
 
 
-def _hash(seed: int, step: int, idx: np.ndarray, lanes: int) -> np.ndarray:
-    """uint64 [n][lanes]: independent words per (seed, step, sample index, lane)."""
+def _hash(seed: int, step: int, idx: np.ndarray, lanes: int, first: int = 1) -> np.ndarray:
+    """uint64 [n][lanes]: independent words per (seed, step, sample index, lane); the lanes are
+    numbered first .. first + lanes - 1."""
     with np.errstate(over="ignore"):
         head = _mix(np.array([(int(seed) * _GOLD + 0x632BE59BD9B4E019) & _M64], dtype=np.uint64))
         head = _mix(head ^ np.uint64((int(step) * _GOLD) & _M64))
         h = _mix(head ^ (idx.astype(np.int64).view(np.uint64) * np.uint64(0xD6E8FEB86659FD93)))
-        lane = (np.arange(1, lanes + 1, dtype=np.uint64) * np.uint64(_GOLD))[None, :]
+        lane = (np.arange(first, first + lanes, dtype=np.uint64) * np.uint64(_GOLD))[None, :]
         return _mix(h[:, None] + lane)
 
 
@@ -90,6 +96,83 @@ def draw(seed: int, step: int, sample_idx, spec, cin: int, dims: int,
         affine[..., 0] = _f32_within(1.0 - a + 2.0 * a * u[..., 0], 1.0 - a, 1.0 + a)
         affine[..., 1] = _f32_within(-a + 2.0 * a * u[..., 1], -a, a)
     return code.astype(np.int32), affine
+
+
+# first hash lane of draw_crop's words: past every lane `draw` can use (1 + 2 cin of them), so a
+# sample's codes and affines are the same with and without --crop
+_CROP_LANE = 1 << 16
+
+
+def _dims3(v) -> Tuple[int, int, int]:
+    v = tuple(int(a) for a in v)
+    if len(v) == 2:
+        v = (1,) + v
+    if len(v) != 3 or min(v) < 1:
+        raise ValueError("spatial size: (D, H, W) or (H, W), all >= 1, got %r" % (v,))
+    return v
+
+
+def draw_crop(seed: int, step: int, sample_idx, stored, patch, mode: str, p_fg: float = 0.0,
+              table=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(origin int32 [n][3] = (d, h, w), used_fg bool [n]) of the training patches of the
+    dataset samples `sample_idx` at global step `step`: `patch` = (D, H, W) (or (H, W)) voxels of
+    the `stored` = (Ds, Hs, Ws) sample.  The same counter hash as :func:`draw` with words of its
+    own: an origin depends on (seed, step, dataset sample index) alone.
+
+    `random`: o_a = floor(u_a (S_a - T_a + 1)) per axis.  `foreground`: with probability `p_fg`,
+    and only for a sample with foreground, entry floor(u min(cnt, R)) of its row of `table` =
+    (fg [N][R], cnt [N]) (datasets.foreground_table) is decoded to a voxel c and
+    o_a = min(max(c_a - T_a // 2, 0), S_a - T_a), so the patch holds c; else the uniform rule."""
+    S, T = np.array(_dims3(stored), dtype=np.int64), np.array(_dims3(patch), dtype=np.int64)
+    if mode not in ("random", "foreground"):
+        raise ValueError("draw_crop: mode random or foreground, got %r" % (mode,))
+    if (T > S).any():
+        raise ValueError("draw_crop: patch %r exceeds the stored sample %r" % (tuple(T), tuple(S)))
+    idx = np.asarray(sample_idx, dtype=np.int64).reshape(-1)
+    u = _unit(_hash(seed, step, idx, 5, first=_CROP_LANE))
+    span = S - T + 1
+    origin = np.minimum(np.floor(u[:, 2:5] * span[None, :]).astype(np.int64), (S - T)[None, :])
+    used = np.zeros(len(idx), dtype=bool)
+    if mode == "foreground":
+        if table is None:
+            raise ValueError("draw_crop: the foreground mode needs the foreground table")
+        fg, cnt = table
+        n = np.minimum(np.asarray(cnt)[idx].astype(np.int64), fg.shape[1])
+        used = (u[:, 0] < float(p_fg)) & (n > 0)
+        j = np.minimum(np.floor(u[:, 1] * n).astype(np.int64), np.maximum(n - 1, 0))
+        lin = np.asarray(fg)[idx, j].astype(np.int64)
+        c = np.stack([lin // (S[1] * S[2]), lin // S[2] % S[1], lin % S[2]], axis=1)
+        at = np.minimum(np.maximum(c - T[None, :] // 2, 0), (S - T)[None, :])
+        origin = np.where(used[:, None], at, origin)
+    return origin.astype(np.int32), used
+
+
+def crop_torch(x, y, origin, patch):
+    """The patches of batch tensors x [n, (Ds,) Hs, Ws, C] and y [n, (Ds,) Hs, Ws, K] (any device)
+    at `origin` [n][3] = (d, h, w), `patch` = (D, H, W) (or (H, W)) voxels each: a per-sample
+    slice, new tensors.  The whole training transform is
+    ``apply_torch(*crop_torch(x, y, origin, patch), code, affine)``."""
+    import torch
+    org = np.asarray(origin.cpu() if isinstance(origin, torch.Tensor) else origin).reshape(-1, 3)
+    n = x.shape[0]
+    if len(org) != n or y.shape[0] != n:
+        raise ValueError("crop_torch: %d origins for %d images and %d targets" % (len(org), n, y.shape[0]))
+    D, H, W = _dims3(patch)
+    three_d = x.dim() == 5
+    S = tuple(x.shape[1:4]) if three_d else (1,) + tuple(x.shape[1:3])
+    if not three_d and D != 1:
+        raise ValueError("crop_torch: 2D samples take a patch of depth 1")
+    for a, (o, t, s) in enumerate(zip(org.T, (D, H, W), S)):
+        if (o < 0).any() or (o + t > s).any():
+            raise ValueError("crop_torch: origins of axis %d outside [0, %d]" % (a, s - t))
+    out = []
+    for src in (x, y):
+        parts = []
+        for i, (d, h, w) in enumerate(org):
+            parts.append(src[i, d:d + D, h:h + H, w:w + W] if three_d else src[i, h:h + H, w:w + W])
+        out.append(torch.stack(parts) if parts else src.new_zeros((0,) + ((D, H, W) if three_d else (H, W))
+                                                                  + (src.shape[-1],)))
+    return out[0], out[1]
 
 
 def inverse_code(code: int) -> int:
@@ -174,3 +257,18 @@ def make_aug(cfg, step: int) -> Optional[Callable[[Sequence[int]], Tuple[np.ndar
     if not names:
         return None
     return lambda idx: draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity)
+
+
+def make_crop_aug(cfg, step: int, stored, table=None):
+    """make_aug's sibling for --crop: dataset sample indices -> (code, affine, origin).  The
+    codes are all zero and the affine None when --augment is off; the origins are draw_crop's."""
+    mode, p_fg = parse_crop(cfg.crop)
+    names = parse_augment(cfg.augment)
+    patch = (cfg.img_size,) * 3 if cfg.dims == 3 else (1, cfg.img_size, cfg.img_size)
+
+    def fn(idx):
+        code, affine = draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity)
+        origin, _ = draw_crop(cfg.seed, step, idx, stored, patch, mode, p_fg, table)
+        return code, affine, origin
+
+    return fn

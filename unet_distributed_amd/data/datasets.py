@@ -167,6 +167,30 @@ def _synthetic_hard(n, img, channels, dims, seed, dtype, out_channels=1):
     return imgs, msks
 
 
+def foreground_table(y, R: int = 32) -> Tuple[np.ndarray, np.ndarray]:
+    """(fg int32 [N][R], cnt int32 [N]) of the targets y [N, (Ds,) Hs, Ws, K]: up to R foreground
+    voxels per sample for --crop foreground (augment.draw_crop) and the sample's foreground
+    count.  Foreground: any target channel >= 0.5.  With n = cnt and the ascending linear voxel
+    indices L[0..n) over (Ds, Hs, Ws), entry j < min(n, R) is L[j] if n <= R, else the evenly
+    spread L[((2 j + 1) n) // (2 R)]; unused entries are -1.  No RNG: one numpy pass per sample
+    when the data is loaded."""
+    N = len(y)
+    fg = np.full((N, R), -1, dtype=np.int32)
+    cnt = np.zeros(N, dtype=np.int32)
+    if N and int(np.prod(y.shape[1:-1])) >= 1 << 31:
+        raise ValueError("foreground_table: a sample of %r voxels does not index with int32" % (y.shape[1:-1],))
+    j = np.arange(R, dtype=np.int64)
+    for i in range(N):
+        L = np.flatnonzero((np.asarray(y[i]) >= 0.5).any(axis=-1))
+        n = len(L)
+        cnt[i] = n
+        if n <= R:
+            fg[i, :n] = L
+        else:
+            fg[i] = L[((2 * j + 1) * n) // (2 * R)]
+    return fg, cnt
+
+
 class EpochSampler:
     """Shared-seed epoch shuffling and per-rank sharding of global batches."""
 

@@ -11,15 +11,20 @@ for sequential reads.  ``--num_threads`` (README.md:63) sizes the gather pool.
 import numpy as np
 import torch
 
-from .augment import apply_torch
+from .augment import apply_torch, crop_torch
 
 
 class BatchLoader:
-    def __init__(self, x: np.ndarray, y: np.ndarray, per_rank: int, threads: int = 8, pin: bool = False):
+    def __init__(self, x: np.ndarray, y: np.ndarray, per_rank: int, threads: int = 8, pin: bool = False,
+                 patch=None):
+        """`patch`: optional (D, H, W) of the training patches (--crop): the staging buffers
+        are patch-sized and `gather` takes the patch origins."""
         self.x, self.y = x, y
         self.threads = max(1, int(threads))
-        self.bx = torch.empty((per_rank,) + tuple(x.shape[1:]), dtype=torch.float32, pin_memory=pin)
-        self.by = torch.empty((per_rank,) + tuple(y.shape[1:]), dtype=torch.float32, pin_memory=pin)
+        self.patch = None if patch is None else tuple(int(v) for v in patch)
+        sp = tuple(x.shape[1:-1]) if patch is None else self.patch[3 - (x.ndim - 2):]
+        self.bx = torch.empty((per_rank,) + sp + (x.shape[-1],), dtype=torch.float32, pin_memory=pin)
+        self.by = torch.empty((per_rank,) + sp + (y.shape[-1],), dtype=torch.float32, pin_memory=pin)
         self._native = None
         try:
             from .. import native
@@ -38,7 +43,23 @@ class BatchLoader:
         else:
             dst.numpy()[:n] = src[idx]
 
-    def gather(self, idx: np.ndarray):
+    def _gather_patches(self, src: np.ndarray, idx: np.ndarray, origin: np.ndarray, dst: torch.Tensor):
+        """dst[i] = the patch of sample idx[i] at origin[i]: only the slice is read and copied."""
+        out = dst.numpy()
+        D, H, W = self.patch
+        for i, (n, (d, h, w)) in enumerate(zip(idx, origin)):
+            out[i] = src[n, d:d + D, h:h + H, w:w + W] if src.ndim == 5 else src[n, h:h + H, w:w + W]
+
+    def gather(self, idx: np.ndarray, origin=None):
+        """`origin` (a patch loader): int [n][3] patch origins of the samples `idx`, which are
+        taken in the order given (the feeder's sorted order)."""
+        if self.patch is not None:
+            if origin is None or len(origin) != len(idx):
+                raise ValueError("patch loader: one origin per sample")
+            idx, origin = np.asarray(idx), np.asarray(origin).reshape(-1, 3)
+            self._gather_patches(self.x, idx, origin, self.bx)
+            self._gather_patches(self.y, idx, origin, self.by)
+            return self.bx, self.by
         idx = np.sort(np.asarray(idx))
         self._gather(self.x, idx, self.bx)
         self._gather(self.y, idx, self.by)
@@ -49,20 +70,28 @@ class ResidentBatch:
     """A batch of the HBM-resident dataset named by sample index: the native backend
     gathers and casts it into its input buffers in one kernel; anything else asks
     for the tensors.  `aug`: optional augmentation parameters of the batch on the
-    device, (code int32 [n], affine float32 [n][Cin][2] or None) (data/augment.py)."""
+    device, (code int32 [n], affine float32 [n][Cin][2] or None) (data/augment.py).  `crop`:
+    optional (origin int32 [n][3] on the device, patch dims (D, H, W)): the batch is the patch
+    of each stored sample at its origin (--crop), cropped before it is augmented."""
 
-    def __init__(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, aug=None):
+    def __init__(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, aug=None, crop=None):
         self.x_all, self.y_all, self.idx = x_all, y_all, idx
         self.aug = aug
+        self.crop = crop
 
     def tensors(self):
         x, y = self.x_all.index_select(0, self.idx), self.y_all.index_select(0, self.idx)
+        if self.crop is not None:
+            x, y = crop_torch(x, y, *self.crop)
         if self.aug is not None:
             x, y = apply_torch(x, y, *self.aug)
         return x, y
 
     @property
     def npix(self) -> int:
+        if self.crop is not None:
+            d, h, w = self.crop[1]
+            return int(self.idx.numel()) * d * h * w * int(self.y_all.shape[-1])
         return int(self.idx.numel()) * int(self.y_all[0].numel())
 
 
@@ -80,9 +109,12 @@ class DeviceFeeder:
     """
 
     def __init__(self, x: np.ndarray, y: np.ndarray, per_rank: int, device, threads: int = 8,
-                 mode: str = "auto", budget_frac: float = 0.25):
+                 mode: str = "auto", budget_frac: float = 0.25, patch=None):
+        """`patch`: optional (D, H, W) of the training patches (--crop): every batch is then
+        cut out of the stored samples at the origins its `aug` callable returns."""
         self.device = torch.device(device)
         self.per_rank = per_rank
+        self.patch = None if patch is None else tuple(int(v) for v in patch)
         nbytes = (x.size + y.size) * 4
         resident = False
         if self.device.type == "cuda":
@@ -97,32 +129,45 @@ class DeviceFeeder:
             self.y = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).to(self.device)
             return
         pin = self.device.type == "cuda"
-        self.loaders = [BatchLoader(x, y, per_rank, threads, pin) for _ in range(2 if pin else 1)]
+        self.loaders = [BatchLoader(x, y, per_rank, threads, pin, self.patch) for _ in range(2 if pin else 1)]
         self.events = [None] * len(self.loaders)
         self.k = 0
 
-    def _upload(self, sorted_idx: np.ndarray, code: np.ndarray, affine):
+    def _upload(self, sorted_idx: np.ndarray, code: np.ndarray, affine, origin=None):
         """Index tensor and augmentation parameters in one small non-blocking copy:
-        [idx int64 | affine fp32 | code int32] -> (idx, (code, affine)) device views."""
+        [idx int64 | affine fp32 | code int32 | origin int32] -> (idx, (code, affine)) device
+        views, and with `origin` (int [n][3], --crop) the origin view as a third item."""
         n = len(sorted_idx)
         af = np.ascontiguousarray(affine, dtype=np.float32) if affine is not None else np.empty(0, np.float32)
         parts = [sorted_idx.view(np.uint8), af.reshape(-1).view(np.uint8),
                  np.ascontiguousarray(code, dtype=np.int32).view(np.uint8)]
+        if origin is not None:
+            parts.append(np.ascontiguousarray(origin, dtype=np.int32).reshape(-1).view(np.uint8))
         buf = torch.from_numpy(np.concatenate(parts)).to(self.device, non_blocking=True)
         na = parts[1].size
         ii = buf[:8 * n].view(torch.int64)
         af = buf[8 * n:8 * n + na].view(torch.float32).view(affine.shape) if affine is not None else None
-        return ii, (buf[8 * n + na:].view(torch.int32), af)
+        cd = buf[8 * n + na:8 * n + na + 4 * n].view(torch.int32)
+        if origin is None:
+            return ii, (cd, af)
+        return ii, (cd, af), buf[8 * n + na + 4 * n:].view(torch.int32).view(n, 3)
 
     def get(self, idx: np.ndarray, lazy: bool = False, aug=None):
         """(x, y) of the samples `idx`; lazy (resident data only): a ResidentBatch
         for a backend that gathers it itself.  `aug`: optional callable, sorted dataset
         sample indices -> (code, affine) (data/augment.py): the batch is augmented with
-        them (a ResidentBatch carries them for the backend's gather kernel)."""
+        them (a ResidentBatch carries them for the backend's gather kernel).  A feeder with
+        `patch` needs `aug` to return (code, affine, origin) (augment.make_crop_aug): the batch
+        is the patches at the origins, cropped first and then augmented."""
         if aug is None:
+            if self.patch is not None:
+                raise ValueError("a cropping feeder needs the per-step origins (aug)")
             return self._get(idx, lazy)
         si = np.sort(np.asarray(idx, dtype=np.int64))       # (the order every path below feeds)
-        code, affine = aug(si)
+        drawn = aug(si)
+        if self.patch is not None:
+            return self._get_crop(si, lazy, *drawn)
+        code, affine = drawn
         if self.resident:
             ii, dev = self._upload(si, code, affine)
             if lazy:
@@ -130,7 +175,18 @@ class DeviceFeeder:
             return apply_torch(self.x.index_select(0, ii), self.y.index_select(0, ii), code, affine)
         return apply_torch(*self._get(idx, False), code, affine)
 
-    def _get(self, idx: np.ndarray, lazy: bool):
+    def _get_crop(self, si: np.ndarray, lazy: bool, code, affine, origin):
+        origin = np.ascontiguousarray(origin, dtype=np.int32).reshape(len(si), 3)
+        if self.resident:
+            ii, dev, org = self._upload(si, code, affine, origin)
+            if lazy:
+                return ResidentBatch(self.x, self.y, ii, dev, (org, self.patch)), None
+            x, y = crop_torch(self.x.index_select(0, ii), self.y.index_select(0, ii), origin, self.patch)
+            return apply_torch(x, y, code, affine)
+        # streamed: the host copies each sample's patch into the patch-sized staging buffers
+        return apply_torch(*self._get(si, False, origin), code, affine)
+
+    def _get(self, idx: np.ndarray, lazy: bool, origin=None):
         if self.resident:
             ii = torch.from_numpy(np.sort(np.asarray(idx, dtype=np.int64))).to(self.device, non_blocking=True)
             if lazy:
@@ -140,7 +196,7 @@ class DeviceFeeder:
         self.k = (self.k + 1) % len(self.loaders)
         if self.events[k] is not None:
             self.events[k].synchronize()        # the copy that last read this buffer is done
-        bx, by = self.loaders[k].gather(idx)
+        bx, by = self.loaders[k].gather(idx, origin) if origin is not None else self.loaders[k].gather(idx)
         if self.device.type != "cuda":
             return bx.clone(), by.clone()
         gx = bx.to(self.device, non_blocking=True)

@@ -190,12 +190,19 @@ class TorchBackend:
         return self._filter(self._predict_raw(x), getattr(self.cfg, "eval_threshold", 0.5))[0]
 
     @torch.no_grad()
-    def predict_sliding(self, x, overlap: float = 0.5, blend: str = "gaussian") -> torch.Tensor:
+    def predict_sliding(self, x, overlap: float = 0.5, blend: str = "gaussian", post: bool = True) -> torch.Tensor:
         """Probabilities fp32 [n, (D,) H, W, K] of images of any spatial size: `predict` on
-        overlapping tiles of the model's size, blended (`ops.sliding.sliding_predict_torch`)."""
+        overlapping tiles of the model's size, blended (`ops.sliding.sliding_predict_torch`).
+        post=False: the blended map itself, before the --eval_components filter."""
         T = sliding.tile_shape(self.cfg.img_size, self.spec.dims)
         p = sliding.sliding_predict_torch(self._predict_raw, x.to(self.device), T, self.B, overlap, blend)
-        return self._filter(p, getattr(self.cfg, "eval_threshold", 0.5))[0]
+        return self._filter(p, getattr(self.cfg, "eval_threshold", 0.5))[0] if post else p
+
+    @torch.no_grad()
+    def sliding_filter(self, p, threshold: float = 0.5) -> torch.Tensor:
+        """The --eval_components filter of full-size probabilities p (p itself with the flag
+        off): what `predict_sliding` returns, from its post=False map."""
+        return self._filter(p, threshold)[0]
 
     @torch.no_grad()
     def sliding_components(self, p, threshold: float = 0.5) -> torch.Tensor:
@@ -204,9 +211,11 @@ class TorchBackend:
         return self._filter(p, threshold)[1]
 
     @torch.no_grad()
-    def sliding_stats(self, p, y, threshold: float = 0.5) -> torch.Tensor:
-        """[n][K][6] of full-size probabilities p (`predict_sliding`) against the target y."""
-        return seg_metrics.case_stats_torch(self._filter(p, threshold)[0], y.to(p.device).float(), threshold)
+    def sliding_stats(self, p, y, threshold: float = 0.5, post: bool = True) -> torch.Tensor:
+        """[n][K][6] of full-size probabilities p (`predict_sliding`) against the target y.
+        post=False: of p itself, the --eval_components filter not applied."""
+        return seg_metrics.case_stats_torch(self._filter(p, threshold)[0] if post else p, y.to(p.device).float(),
+                                            threshold)
 
     @torch.no_grad()
     def sliding_surface(self, p, y, threshold: float = 0.5) -> torch.Tensor:
@@ -258,7 +267,9 @@ class NativeBackend:
         self._pp_thr = None
         e.set_loss_scale(grad_scale)
         if hasattr(x, "x_all"):
-            if getattr(x, "aug", None) is not None:
+            if getattr(x, "crop", None) is not None:
+                e.load_indexed(x.x_all, x.y_all, x.idx, aug=x.aug, crop=x.crop)
+            elif getattr(x, "aug", None) is not None:
                 e.load_indexed(x.x_all, x.y_all, x.idx, aug=x.aug)
             else:
                 e.load_indexed(x.x_all, x.y_all, x.idx)
@@ -379,14 +390,15 @@ class NativeBackend:
         return e.probs().clone()
 
     @torch.no_grad()
-    def predict_sliding(self, x, overlap: float = 0.5, blend: str = "gaussian") -> torch.Tensor:
+    def predict_sliding(self, x, overlap: float = 0.5, blend: str = "gaussian", post: bool = True) -> torch.Tensor:
         """Probabilities fp32 [n, (D,) H, W, K] of images of any spatial size, on the device: the
         executor's sliding-window path (`native_engine.run_predict_sliding`: sw_extract, the
         evaluation forward -- with --eval_tta the mean over the transforms -- and sw_blend per
-        batch of tiles, then sw_finish).  The executor's buffer, overwritten by the next call."""
+        batch of tiles, then sw_finish).  The executor's buffer, overwritten by the next call.
+        post=False: the blended map itself, before the --eval_components filter."""
         self._pp_thr = None                   # (the tiles' forwards overwrite the executor's prob)
         p = self.engine.predict_sliding(x.to(self.engine.device), overlap, blend, self.tta)
-        return self._sw_filter(p, getattr(self.cfg, "eval_threshold", 0.5))[0]
+        return self._sw_filter(p, getattr(self.cfg, "eval_threshold", 0.5))[0] if post else p
 
     def _sw_filter(self, p, threshold: float):
         """(p, None) with the filter off, else (filtered p, info) of a full-size map
@@ -403,16 +415,23 @@ class NativeBackend:
         return out, info
 
     @torch.no_grad()
+    def sliding_filter(self, p, threshold: float = 0.5) -> torch.Tensor:
+        """The --eval_components filter of full-size probabilities p (p itself with the flag
+        off): what `predict_sliding` returns, from its post=False map."""
+        return self._sw_filter(p, threshold)[0]
+
+    @torch.no_grad()
     def sliding_components(self, p, threshold: float = 0.5) -> torch.Tensor:
         """int32 [n][K][4] of full-size probabilities p (`predict_sliding`'s result)."""
         _need_policy(self)
         return self._sw_filter(p, threshold)[1]
 
     @torch.no_grad()
-    def sliding_stats(self, p, y, threshold: float = 0.5) -> torch.Tensor:
-        """fp32 [n][K][6] of full-size probabilities p (`predict_sliding`) against the target y."""
+    def sliding_stats(self, p, y, threshold: float = 0.5, post: bool = True) -> torch.Tensor:
+        """fp32 [n][K][6] of full-size probabilities p (`predict_sliding`) against the target y.
+        post=False: of p itself, the --eval_components filter not applied."""
         from .native_engine import sliding_stats
-        return sliding_stats(self.engine, self._sw_filter(p, threshold)[0], y, threshold)
+        return sliding_stats(self.engine, self._sw_filter(p, threshold)[0] if post else p, y, threshold)
 
     @torch.no_grad()
     def sliding_surface(self, p, y, threshold: float = 0.5) -> torch.Tensor:

@@ -34,8 +34,9 @@ import torch
 
 from .. import native
 from ..models.spec import UNetSpec
-from .native_engine import (gather_aug_args, plan_case_stats, plan_case_surface, plan_components, plan_tta,
-                            run_case_stats, run_case_surface, run_components, run_evaluate_tta, run_predict_sliding)
+from .native_engine import (gather_aug_args, gather_crop_args, plan_case_stats, plan_case_surface, plan_components,
+                            plan_tta, run_case_stats, run_case_surface, run_components, run_evaluate_tta,
+                            run_predict_sliding)
 from .params import FlatParams
 from .plan_check import RecordingPlan
 
@@ -392,9 +393,21 @@ class NativeUNetF32:
         self.bufs["x"].view(-1).copy_(x.reshape(-1), non_blocking=True)
         self.target.copy_(y.reshape(-1), non_blocking=True)
 
-    def load_indexed(self, x_all, y_all, idx, stream=None, aug=None):
+    def load_indexed(self, x_all, y_all, idx, stream=None, aug=None, crop=None):
         """`aug`: optional (code, affine) on the device (data/augment.py): one
-        f32_gather_batch_aug launch gathers and transforms the batch (kernels/gather_aug.h)."""
+        f32_gather_batch_aug launch gathers and transforms the batch (kernels/gather_aug.h).
+        `crop`: optional (origin int32 [B][3] on the device, patch dims): one
+        f32_gather_batch_crop launch reads each sample's patch of the larger stored samples and
+        transforms it (kernels/gather_crop.h)."""
+        if crop is not None:
+            cin = self.spec.in_channels
+            K = y_all[0].numel() * cin // x_all[0].numel()
+            assert idx.dtype == torch.int64 and idx.numel() == self.B and x_all.dtype == torch.float32
+            assert y_all.dtype == torch.float32 and x_all.is_contiguous() and y_all.is_contiguous()
+            assert self.target.numel() == self.npix(1) * K and self.bufs["x"].numel() == self.npix(1) * cin
+            ptrs, ints = gather_crop_args(self, x_all, y_all, idx, aug, crop, cin, cin, K)
+            self.C.generic("f32_gather_batch_crop", ptrs, ints, [], native.stream_handle(stream), 0)
+            return
         if aug is not None:
             cin = self.spec.in_channels
             K = y_all[0].numel() * cin // x_all[0].numel()

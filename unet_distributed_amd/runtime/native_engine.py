@@ -2008,16 +2008,23 @@ class NativeUNet:
                              % (y.numel(), self.target.numel(), self.B, self.K))
         self.target.copy_(y.reshape(-1), non_blocking=True)
 
-    def load_indexed(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, stream=None, aug=None):
+    def load_indexed(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, stream=None, aug=None,
+                     crop=None):
         """Batch = samples `idx` (device int64) of the HBM-resident dataset, gathered
         and cast straight into the padded 16-bit input and target (one launch).  `aug`:
         optional (code int32 [B], affine float32 [B][Cin][2] or None) on the device
         (data/augment.py): the same launch flips / rotates each sample and applies its
-        per-channel affine (kernels/gather_aug.h)."""
+        per-channel affine (kernels/gather_aug.h).  `crop`: optional (origin int32 [B][3] on
+        the device, patch dims): the stored samples are larger than the model's input and the
+        launch reads each sample's patch at its origin, then transforms it (kernels/gather_crop.h)."""
         cin = self.spec.in_channels
         P = x_all[0].numel() // cin
         assert idx.dtype == torch.int64 and idx.numel() == self.B and x_all.dtype == torch.float32
         assert y_all[0].numel() == P * self.K and x_all.is_contiguous() and y_all.is_contiguous()
+        if crop is not None:
+            ptrs, ints = gather_crop_args(self, x_all, y_all, idx, aug, crop, cin, self.cpad, self.K)
+            self.C.generic("gather_batch_crop", ptrs, ints, [], native.stream_handle(stream), self.dt_id)
+            return
         if aug is not None:
             ptrs, ints = gather_aug_args(self, x_all, y_all, idx, aug, cin, self.cpad, self.K)
             self.C.generic("gather_batch_aug", ptrs, ints, [], native.stream_handle(stream), self.dt_id)
@@ -2225,6 +2232,32 @@ def gather_aug_args(e, x_all, y_all, idx, aug, cin: int, cpad: int, K: int):
     ptrs = [_ptr(x_all), _ptr(y_all), _ptr(idx), _ptr(code), _ptr(affine) if affine is not None else 0,
             _ptr(e.bufs["x"]), _ptr(e.target)]
     return ptrs, [e.B, D, H, W, cin, cpad, K]
+
+
+def gather_crop_args(e, x_all, y_all, idx, aug, crop, cin: int, cpad: int, K: int):
+    """(ptrs, ints) of an executor's gather_batch_crop / f32_gather_batch_crop launch
+    (bindings.cpp) from the resident dataset [N, (Ds,) Hs, Ws, Cin], `aug` = (code or None,
+    affine or None) or None, and `crop` = (origin int32 [B][3], patch dims (D, H, W))."""
+    origin, patch = crop
+    code, affine = aug if aug is not None else (None, None)
+    Ds = x_all.shape[1] if x_all.dim() == 5 else 1
+    Hs, Ws = x_all.shape[-3], x_all.shape[-2]
+    patch = tuple(int(v) for v in patch)
+    if patch != tuple(e.sdims(1)):
+        raise ValueError("crop patch %r: the executor's input is %r" % (patch, tuple(e.sdims(1))))
+    if (origin.dtype != torch.int32 or tuple(origin.shape) != (e.B, 3) or origin.device != x_all.device
+            or not origin.is_contiguous()):
+        raise ValueError("crop origins: a contiguous int32 [%d][3] tensor on %s" % (e.B, x_all.device))
+    if code is not None and (code.dtype != torch.int32 or code.numel() != e.B or code.device != x_all.device
+                             or not code.is_contiguous()):
+        raise ValueError("augmentation codes: a contiguous int32 [%d] tensor on %s" % (e.B, x_all.device))
+    if affine is not None and (affine.dtype != torch.float32 or tuple(affine.shape) != (e.B, cin, 2)
+                               or affine.device != x_all.device or not affine.is_contiguous()):
+        raise ValueError("augmentation affine: a contiguous float32 [%d][%d][2] tensor on %s"
+                         % (e.B, cin, x_all.device))
+    ptrs = [_ptr(x_all), _ptr(y_all), _ptr(idx), _ptr(origin), _ptr(code) if code is not None else 0,
+            _ptr(affine) if affine is not None else 0, _ptr(e.bufs["x"]), _ptr(e.target)]
+    return ptrs, [e.B, Ds, Hs, Ws, patch[0], patch[1], patch[2], cin, cpad, K]
 
 
 def plan_case_stats(e, kind: str) -> None:

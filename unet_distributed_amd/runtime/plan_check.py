@@ -118,6 +118,12 @@ def _generic_write_spans(kind: str, p: List[int], ints: List[int]) -> List[Tuple
         B, D, H, W, _, cpad, K = ints[:7]
         eb = 4 if kind.startswith("f32") else 2
         return [(p[5], B * D * H * W * cpad * eb), (p[6], B * D * H * W * K * eb)]
+    # cropping batch gather (B, Ds, Hs, Ws, D, H, W, Cin, Cpad, K in ints): the same two buffers,
+    # of the patch's size
+    if kind in ("gather_batch_crop", "f32_gather_batch_crop") and len(p) > 7 and len(ints) >= 10:
+        B, _, _, _, D, H, W, _, cpad, K = ints[:10]
+        eb = 4 if kind.startswith("f32") else 2
+        return [(p[6], B * D * H * W * cpad * eb), (p[7], B * D * H * W * K * eb)]
     # test-time augmentation: the fp32 accumulator (N, D, H, W, K in ints); the finish (total
     # elements in ints) rewrites prob and writes one row of 4 floats per block and the 4 sums
     if kind == "tta_acc" and len(p) > 1 and len(ints) >= 5:
@@ -225,6 +231,8 @@ def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], Li
         return _sel(p, [0]), _sel(p, [1, 2, 3])
     if kind in ("gather_batch_aug", "f32_gather_batch_aug"):
         return [q for q in _sel(p, [0, 1, 2, 3, 4]) if q], _sel(p, [5, 6])
+    if kind in ("gather_batch_crop", "f32_gather_batch_crop"):
+        return [q for q in _sel(p, [0, 1, 2, 3, 4, 5]) if q], _sel(p, [6, 7])
     if kind == "tta_acc":                # (write mode reads no element of the accumulator)
         return _sel(p, [0, 1] if len(ints) > 6 and ints[6] else [0]), _sel(p, [1])
     if kind in ("tta_finish", "f32_tta_finish"):

@@ -24,9 +24,9 @@ import numpy as np
 import torch
 
 from .. import settings
-from ..config import parse_augment, parse_tta
+from ..config import parse_augment, parse_crop, parse_tta
 from ..data import datasets
-from ..data.augment import make_aug, tta_codes
+from ..data.augment import make_aug, make_crop_aug, tta_codes
 from ..data.loader import DeviceFeeder
 from ..models import reference
 from ..models.spec import spec_from_config
@@ -197,11 +197,12 @@ class Trainer:
         cfg = self.cfg
         if cfg.synthetic:
             n_tr = max(cfg.synthetic_train, cfg.batch_size)
-            self.x_train, self.y_train = datasets.synthetic_brats(n_tr, cfg.img_size, cfg.in_channels,
+            size = cfg.synthetic_size or cfg.img_size       # stored side of the train and test images
+            self.x_train, self.y_train = datasets.synthetic_brats(n_tr, size, cfg.in_channels,
                                                                   cfg.dims, seed=cfg.seed,
                                                                   difficulty=cfg.synthetic_difficulty,
                                                                   out_channels=cfg.out_channels)
-            self.x_test, self.y_test = datasets.synthetic_brats(cfg.synthetic_test, cfg.img_size,
+            self.x_test, self.y_test = datasets.synthetic_brats(cfg.synthetic_test, size,
                                                                 cfg.in_channels, cfg.dims, seed=cfg.seed + 1,
                                                                 difficulty=cfg.synthetic_difficulty,
                                                                 out_channels=cfg.out_channels)
@@ -215,10 +216,33 @@ class Trainer:
             print("Training masks shape:  {}".format(self.y_train.shape))
             print("Testing images shape:  {}".format(self.x_test.shape))
             print("Testing masks shape:   {}".format(self.y_test.shape))
+        # --crop: training patches of the model's size out of larger stored samples; a test set
+        # that is not of the model's size is scored through sliding windows
+        model = (cfg.img_size,) * cfg.dims
+        stored, tested = tuple(self.x_train.shape[1:-1]), tuple(self.x_test.shape[1:-1])
+        self.crop_mode, self.crop_p = parse_crop(cfg.crop)
+        self.crop_patch = self.crop_table = None
+        if len(stored) != cfg.dims or len(tested) != cfg.dims:
+            raise SystemExit("--dims %d: the stored samples are %s (train) and %s (test)"
+                             % (cfg.dims, " x ".join(map(str, stored)), " x ".join(map(str, tested))))
+        if not self.crop_mode and stored != model:
+            raise SystemExit("the stored training images are %s and the model's input is %s: pass --crop "
+                             "random|foreground to train on patches (or --img_size to match)"
+                             % (" x ".join(map(str, stored)), " x ".join(map(str, model))))
+        if self.crop_mode:
+            if any(s < t for s, t in zip(stored, model)):
+                raise SystemExit("--crop: the stored training images (%s) are smaller than the patch (%s); "
+                                 "padding is not supported" % (" x ".join(map(str, stored)),
+                                                               " x ".join(map(str, model))))
+            self.crop_patch = (1,) * (3 - cfg.dims) + model
+            self.crop_stored = (1,) * (3 - cfg.dims) + stored
+            if self.crop_mode == "foreground":
+                self.crop_table = datasets.foreground_table(self.y_train)
+        self.eval_sliding = tested != model
         self.sampler = datasets.EpochSampler(len(self.x_train), cfg.batch_size, self.rank, self.world, cfg.seed)
         self.num_batches = self.sampler.num_batches
         self.feeder = DeviceFeeder(self.x_train, self.y_train, self.per_rank, self.device,
-                                   threads=min(cfg.num_threads, 16), mode=cfg.data_on_device)
+                                   threads=min(cfg.num_threads, 16), mode=cfg.data_on_device, patch=self.crop_patch)
         if self.is_chief:
             print("Training data: %s" % ("resident in device memory" if self.feeder.resident
                                          else "streamed from host (pinned, double-buffered)"))
@@ -226,6 +250,12 @@ class Trainer:
                 names = parse_augment(cfg.augment)
                 print("Training augmentation: %s%s" % (", ".join(names), " (amplitude %g)" % cfg.augment_intensity
                                                        if "intensity" in names else ""))
+            if self.crop_mode:
+                print("Training patches: %s of %s, %s" % (
+                    " x ".join(map(str, model)), " x ".join(map(str, stored)),
+                    "foreground %.2f" % self.crop_p if self.crop_mode == "foreground" else "uniform"))
+            if self.eval_sliding:
+                print("Evaluation: sliding window, overlap %g, %s" % (cfg.eval_overlap, cfg.eval_blend))
             if cfg.eval_tta:
                 print("Evaluation TTA: %s (%d passes)" % (", ".join(parse_tta(cfg.eval_tta)),
                                                           len(tta_codes(cfg.eval_tta, cfg.dims))))
@@ -237,6 +267,10 @@ class Trainer:
         # native backend + resident data: the backend gathers the batch itself (one
         # gather+cast kernel into its input buffers, no fp32 batch copy)
         lazy = self.backend.name == "native"
+        if self.crop_mode:
+            # --crop: per-sample patch origins from (seed, step, dataset index), with the codes and affines
+            return self.feeder.get(idx, lazy=lazy, aug=make_crop_aug(self.cfg, step, self.crop_stored,
+                                                                     self.crop_table))
         if not self.cfg.augment:
             return self.feeder.get(idx, lazy=lazy)
         # --augment: per-sample parameters from (seed, step, dataset index) ride on the gather
@@ -260,7 +294,15 @@ class Trainer:
         `case_dice` and HD95 are of the connected-component-filtered map (the per-class soft Dice
         too; the pooled batch metrics are not), `per_class["components"]` /
         `per_class["components_kept"]` are the mean per case of the component counts before and
-        after the filter and the dict carries `components`, the flag string."""
+        after the filter and the dict carries `components`, the flag string.
+
+        A test set that is not of the model's size goes through sliding windows: per chunk of the
+        same `per_rank` images (the tail a shorter chunk) `predict_sliding` at --eval_overlap /
+        --eval_blend, then `sliding_stats`, `sliding_surface` and `sliding_components` at the
+        images' own size.  The pooled block is of each full chunk's sums I, St, Sp (the un-filtered
+        `sliding_stats` over its cases and classes) and the BCE of the blended probabilities
+        (logs clamped at -100), and the dict carries `sliding` = {overlap, blend}."""
+        sliding = getattr(self, "eval_sliding", False)
         n = len(self.x_test)
         B = self.per_rank
         nbatches = n // B
@@ -290,7 +332,31 @@ class Trainer:
             return (torch.from_numpy(np.ascontiguousarray(self.x_test[lo:hi])).to(self.device),
                     torch.from_numpy(np.ascontiguousarray(self.y_test[lo:hi])).to(self.device))
 
+        def slide(lo, hi, full):
+            x, y = load(lo, hi)
+            p = self.backend.predict_sliding(x, self.cfg.eval_overlap, self.cfg.eval_blend, post=False)
+            if full:
+                raw = self.backend.sliding_stats(p, y, thr, post=False)
+                bce = torch.nn.functional.binary_cross_entropy(p, y.to(p.device).float(), reduction="sum")
+                s4 = torch.cat([raw[..., :3].double().sum(dim=(0, 1)), bce.double().reshape(1)])
+                m = metrics_from_sums(s4, y.numel(), self.cfg)
+                acc[:] += torch.tensor([m["loss"], m["dice"], m["sensitivity"], m["specificity"], 1.0],
+                                       dtype=torch.float64, device=self.device)
+            if want_cc:                         # (filtered once: the calls below recognise their own map)
+                p = self.backend.sliding_filter(p, thr)
+            stats = raw if full and not want_cc else self.backend.sliding_stats(p, y, thr)
+            if full:
+                cls[:K] += seg_metrics.soft_dice(stats)
+            hard(stats, y[0].numel() // K)
+            if want_hd:
+                surface(self.backend.sliding_surface(p, y, thr), y)
+            if want_cc:
+                comps(self.backend.sliding_components(p, thr))
+
         for b in range(self.rank, nbatches, self.world):
+            if sliding:
+                slide(b * B, (b + 1) * B, True)
+                continue
             x, y = load(b * B, (b + 1) * B)
             m = metrics_from_sums(self.backend.eval_sums(x, y), y.numel(), self.cfg)
             acc += torch.tensor([m["loss"], m["dice"], m["sensitivity"], m["specificity"], 1.0],
@@ -302,7 +368,9 @@ class Trainer:
                 surface(self.backend.last_eval_surface(thr), y)
             if want_cc:
                 comps(self.backend.last_eval_components(thr))
-        if n % B and self.rank == nbatches % self.world:
+        if sliding and n % B and self.rank == nbatches % self.world:
+            slide(nbatches * B, n, False)
+        elif n % B and self.rank == nbatches % self.world:
             x, y = load(nbatches * B, n)
             hard(self.backend.eval_stats(x, y, thr), y[0].numel() // K)
             if want_hd:
@@ -335,6 +403,8 @@ class Trainer:
             m["components"] = self.cfg.eval_components
         if self.cfg.eval_tta:                   # every forward above was the mean over this many passes
             m["tta"] = len(tta_codes(self.cfg.eval_tta, self.cfg.dims))
+        if sliding:
+            m["sliding"] = {"overlap": float(self.cfg.eval_overlap), "blend": self.cfg.eval_blend}
         return m
 
     # ------------------------------------------------------------------ step
