@@ -104,8 +104,10 @@ class Config:
     loss_scale: float = 0.0          # fp16 static loss scale (0 = dynamic)
     eval_threshold: float = 0.5      # probability threshold of the per-case (hard) evaluation metrics
     eval_hd95: bool = False          # evaluation also reports the per-case 95th-percentile Hausdorff distance
-    augment: str = ""                # training batches only: comma-separated subset of flip, rot90, intensity
+    augment: str = ""                # training batches only: comma-separated subset of flip, rot90, intensity, rotate, scale
     augment_intensity: float = 0.1   # intensity: scale in [1-a, 1+a], shift in [-a, a] per (sample, channel)
+    augment_rotate: float = 30.0     # rotate: angle uniform in [-r, r] degrees per sample, r in (0, 180]
+    augment_scale: float = 0.25      # scale: zoom log-uniform in [1/(1+a), 1+a] per sample, a in (0, 1]
     eval_tta: str = ""               # evaluation only: mean prediction over flip and / or rot90 (comma-separated)
     eval_components: str = ""        # evaluation only: connected-component filter, comma list of largest, min:V
     crop: str = ""                   # training patches of img_size from larger stored images: random | foreground[:P]
@@ -136,7 +138,8 @@ _CHOICES = {
 }
 
 
-AUGMENT_NAMES = ("flip", "rot90", "intensity")
+AUGMENT_NAMES = ("flip", "rot90", "intensity", "rotate", "scale")
+SPATIAL_NAMES = ("rotate", "scale")  # the transforms that resample the image (data/augment.py draw_spatial)
 
 
 def parse_augment(s: str) -> tuple:
@@ -281,5 +284,11 @@ def validate(cfg: Config) -> None:
         raise SystemExit("--eval_blend must be constant or gaussian")
     if not 0.0 <= cfg.augment_intensity < 1.0:
         raise SystemExit("--augment_intensity must be in [0, 1)")
+    if not 0.0 < cfg.augment_rotate <= 180.0:
+        raise SystemExit("--augment_rotate must be in (0, 180]: the largest angle in degrees, got %r"
+                         % (cfg.augment_rotate,))
+    if not 0.0 < cfg.augment_scale <= 1.0:
+        raise SystemExit("--augment_scale must be in (0, 1]: the zoom is drawn from [1/(1+a), 1+a], got %r"
+                         % (cfg.augment_scale,))
     if cfg.mode == 5 and cfg.out_channels > 3:
         raise SystemExit("--mode 5 has three nested regions: --out_channels must be 1..3")

@@ -41,6 +41,15 @@ const char* gather_crop_check(long long B, long long Ds, long long Hs, long long
 hipError_t gather_batch_crop_launch(const float* x_all, const float* y_all, const long long* idx, const int* origin,
                                     const int* code, const float* affine, int B, int Ds, int Hs, int Ws, int D, int H,
                                     int W, int Cin, int Cpad, int K, void* xb, void* tb, hipStream_t s);
+// gather_batch_crop resampled through a per-sample Q16 matrix in the (H, W) plane (mat int32
+// [B][4], entries clamped into [-2^18, 2^18] by the kernel): bilinear image, nearest target,
+// zero outside the stored image (gather_warp.h); origin may be null (= 0), code may be null (= 0)
+const char* gather_warp_check(long long B, long long Ds, long long Hs, long long Ws, long long D, long long H,
+                              long long W, long long Cin, long long Cpad, long long K);
+hipError_t gather_batch_warp_launch(const float* x_all, const float* y_all, const long long* idx, const int* origin,
+                                    const int* code, const int* mat, const float* affine, int B, int Ds, int Hs,
+                                    int Ws, int D, int H, int W, int Cin, int Cpad, int K, void* xb, void* tb,
+                                    hipStream_t s);
 // code: optional uint32 per (pooled pixel, 8 channels) = first-argmax index per channel
 // (2 / 3 bits); the backward reads it instead of x when non-null
 hipError_t maxpool2_fwd_launch(const void* x, int N, int D, int H, int W, int C, int dims3, void* y, void* code,
@@ -226,6 +235,11 @@ hipError_t f32_gather_batch_crop_launch(const float* x_all, const float* y_all, 
                                         const int* origin, const int* code, const float* affine, int B, int Ds, int Hs,
                                         int Ws, int D, int H, int W, int Cin, int Cpad, int K, float* xb, float* tb,
                                         hipStream_t s);
+// gather_batch_warp with fp32 outputs (f32_gather_warp.hip)
+hipError_t f32_gather_batch_warp_launch(const float* x_all, const float* y_all, const long long* idx,
+                                        const int* origin, const int* code, const int* mat, const float* affine, int B,
+                                        int Ds, int Hs, int Ws, int D, int H, int W, int Cin, int Cpad, int K,
+                                        float* xb, float* tb, hipStream_t s);
 // surf_dist with an fp32 target (f32_surf_dist.hip)
 hipError_t f32_surf_dist_launch(const float* prob, const float* t, int N, int D, int H, int W, int K, float thr,
                                 int* field, int* surf, hipStream_t s);

@@ -21,13 +21,20 @@ batch gather).
 own (the codes and affines above do not change), :func:`crop_torch` is the crop in plain
 torch, and the whole transform is ``apply_torch(*crop_torch(x, y, origin, patch), code,
 affine)`` -- the oracle of ``csrc/kernels/gather_crop.h``.
+
+``--augment rotate,scale`` adds a 2 x 2 matrix per sample in Q16, rotation by any angle and
+isotropic zoom in the (H, W) plane: :func:`draw_spatial` draws it from hash words of its own,
+:func:`warp_torch` resamples the patch through it straight from the stored sample (bilinear
+image, nearest target, zero outside the image) in integer coordinates, and the whole transform
+is ``apply_torch(*warp_torch(x, y, origin, patch, mat), code, affine)`` -- the oracle of
+``csrc/kernels/gather_warp.h``.
 """
 
 from typing import Callable, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..config import parse_augment, parse_crop, parse_tta
+from ..config import SPATIAL_NAMES, parse_augment, parse_crop, parse_tta
 
 FW, FH, T, FD = 1, 2, 4, 8
 # np.rot90(m, k) of the (H, W) plane for k = 0..3 as codes
@@ -175,6 +182,113 @@ def crop_torch(x, y, origin, patch):
     return out[0], out[1]
 
 
+# first hash lane of draw_spatial's words: past draw's and draw_crop's, so codes, affines and
+# origins are the same with and without rotate / scale
+_SPATIAL_LANE = 1 << 17
+MAT_ONE = 1 << 16                    # 1.0 in the Q16 of a warp matrix
+MAT_MAX = 1 << 18                    # every entry is clamped into [-MAT_MAX, MAT_MAX] before use
+
+
+def draw_spatial(seed: int, step: int, sample_idx, names, rotate_deg: float = 30.0,
+                 scale_a: float = 0.25) -> np.ndarray:
+    """mat int32 [n][4] = (a00, a01, a10, a11) in Q16 of the dataset samples `sample_idx` at
+    global step `step`: the 2 x 2 matrix that maps an output offset from the patch centre to a
+    source offset from it, in the (H, W) plane.  The same counter hash as :func:`draw` with two
+    words of its own.  `names`: the --augment string or its parsed names; with `rotate`
+    theta = (2 u0 - 1) rotate_deg pi / 180, else 0; with `scale` the zoom z =
+    (1 + scale_a) ** (2 u1 - 1), log-uniform in [1 / (1 + a), 1 + a], else 1;
+    a00 = a11 = rint(65536 cos(theta) / z), a10 = rint(65536 sin(theta) / z), a01 = -a10."""
+    names = parse_augment(names) if isinstance(names, str) else tuple(names)
+    idx = np.asarray(sample_idx, dtype=np.int64).reshape(-1)
+    u = _unit(_hash(seed, step, idx, 2, first=_SPATIAL_LANE))
+    theta = (2.0 * u[:, 0] - 1.0) * (float(rotate_deg) * np.pi / 180.0) if "rotate" in names else np.zeros(len(idx))
+    z = (1.0 + float(scale_a)) ** (2.0 * u[:, 1] - 1.0) if "scale" in names else np.ones(len(idx))
+    c, s = np.rint(MAT_ONE * np.cos(theta) / z), np.rint(MAT_ONE * np.sin(theta) / z)
+    return np.stack([c, -s, s, c], axis=1).astype(np.int32)
+
+
+def mat_of_code(code: int) -> np.ndarray:
+    """int32 [4]: the exact warp matrix of in-plane code `code` (0..7): entries 0 or +-65536, so
+    warping with it and code 0 is apply_torch with `code`."""
+    code = int(code)
+    if not 0 <= code < 8:
+        raise ValueError("mat_of_code: an in-plane code 0..7, got %r" % (code,))
+    sh, sw = (-MAT_ONE if code & FH else MAT_ONE), (-MAT_ONE if code & FW else MAT_ONE)
+    return np.array([0, sh, sw, 0] if code & T else [sh, 0, 0, sw], dtype=np.int32)
+
+
+def warp_torch(x, y, origin, patch, mat):
+    """The resampled patches of batch tensors x [n, (Ds,) Hs, Ws, C] and y [n, (Ds,) Hs, Ws, K]
+    (any device): `patch` = (D, H, W) (or (H, W)) voxels at `origin` [n][3] = (d, h, w) (None: 0;
+    clamped into the sample), read through `mat` int [n][4] (draw_spatial; entries clamped into
+    [-2^18, 2^18]).  New tensors [n, (D,) H, W, C / K]: the image bilinear, the target nearest,
+    both zero outside the stored image; depth is neither rotated nor interpolated.
+
+    The geometry is integer: with u = 2 h - (H-1), v = 2 w - (W-1),
+    Qh = (oh << 17) + (H-1) 65536 + a00 u + a01 v and Qw = (ow << 17) + (W-1) 65536 + a10 u + a11 v
+    are source coordinates in 2^-17 pixel.  Image: ih = Qh >> 17, fh = Qh & 0x1FFFF, taps
+    p_ij = x[ih + i][iw + j] (0 outside), weights wh1 = fh 2^-17, wh0 = (131072 - fh) 2^-17,
+    r0 = p00 ww0 + p01 ww1, r1 = p10 ww0 + p11 ww1, value = r0 wh0 + r1 wh1 -- one fp32 tensor
+    op per product and per sum, each rounding once.  Target: y at ((Qh + 65536) >> 17,
+    (Qw + 65536) >> 17).  The whole training transform is
+    ``apply_torch(*warp_torch(x, y, origin, patch, mat), code, affine)`` straight from the stored
+    samples -- taps outside the patch rectangle read the stored image -- and the oracle of
+    ``csrc/kernels/gather_warp.h``."""
+    import torch
+    n = x.shape[0]
+    D, H, W = _dims3(patch)
+    three_d = x.dim() == 5
+    Ds, Hs, Ws = tuple(x.shape[1:4]) if three_d else (1,) + tuple(x.shape[1:3])
+    if not three_d and D != 1:
+        raise ValueError("warp_torch: 2D samples take a patch of depth 1")
+    if D > Ds or H > Hs or W > Ws:
+        raise ValueError("warp_torch: patch %r exceeds the stored sample %r" % ((D, H, W), (Ds, Hs, Ws)))
+    m = np.asarray(mat.cpu() if isinstance(mat, torch.Tensor) else mat).reshape(-1, 4).astype(np.int64)
+    if origin is None:
+        org = np.zeros((n, 3), dtype=np.int64)
+    else:
+        org = np.asarray(origin.cpu() if isinstance(origin, torch.Tensor) else origin).reshape(-1, 3).astype(np.int64)
+    if len(m) != n or len(org) != n or y.shape[0] != n:
+        raise ValueError("warp_torch: %d matrices and %d origins for %d images and %d targets"
+                         % (len(m), len(org), n, y.shape[0]))
+    dev = x.device
+    m = torch.from_numpy(np.clip(m, -MAT_MAX, MAT_MAX)).to(dev)
+    org = torch.from_numpy(np.clip(org, 0, np.array([Ds - D, Hs - H, Ws - W], dtype=np.int64)[None, :])).to(dev)
+    u = (2 * torch.arange(H, dtype=torch.int64, device=dev) - (H - 1)).view(1, H, 1)
+    v = (2 * torch.arange(W, dtype=torch.int64, device=dev) - (W - 1)).view(1, 1, W)
+    a = [m[:, e].view(n, 1, 1) for e in range(4)]
+    qh = (org[:, 1].view(n, 1, 1) << 17) + (H - 1) * 65536 + a[0] * u + a[1] * v
+    qw = (org[:, 2].view(n, 1, 1) << 17) + (W - 1) * 65536 + a[2] * u + a[3] * v
+    # the D slices of every sample, pixels flattened: [n, D, Hs Ws, C]
+    dsel = org[:, 0].view(n, 1) + torch.arange(D, dtype=torch.int64, device=dev).view(1, D)
+
+    def slices(src):
+        s5 = src if three_d else src.unsqueeze(1)
+        s5 = s5.reshape(n, Ds, Hs * Ws, src.shape[-1])
+        return s5.gather(1, dsel.view(n, D, 1, 1).expand(n, D, Hs * Ws, src.shape[-1]))
+
+    def taps(src, r, c):
+        """src [n, D, Hs Ws, C] at rows r and columns c [n, H, W]: [n, D, H, W, C], 0 outside."""
+        ok = (r >= 0) & (r < Hs) & (c >= 0) & (c < Ws)
+        lin = (r.clamp(0, Hs - 1) * Ws + c.clamp(0, Ws - 1)).view(n, 1, H * W, 1)
+        g = src.gather(2, lin.expand(n, D, H * W, src.shape[-1])).view(n, D, H, W, src.shape[-1])
+        return torch.where(ok.view(n, 1, H, W, 1), g, torch.zeros((), dtype=src.dtype, device=dev))
+
+    xs, ys = slices(x), slices(y)
+    ih, iw = qh >> 17, qw >> 17
+    fh, fw = qh & 0x1FFFF, qw & 0x1FFFF
+    sh = (n, 1, H, W, 1)
+    wh1, wh0 = (fh.float() * 2.0 ** -17).view(sh), ((131072 - fh).float() * 2.0 ** -17).view(sh)
+    ww1, ww0 = (fw.float() * 2.0 ** -17).view(sh), ((131072 - fw).float() * 2.0 ** -17).view(sh)
+    r0 = taps(xs, ih, iw) * ww0 + taps(xs, ih, iw + 1) * ww1
+    r1 = taps(xs, ih + 1, iw) * ww0 + taps(xs, ih + 1, iw + 1) * ww1
+    xo = r0 * wh0 + r1 * wh1
+    yo = taps(ys, (qh + 65536) >> 17, (qw + 65536) >> 17)
+    if not three_d:
+        xo, yo = xo.squeeze(1), yo.squeeze(1)
+    return xo.contiguous(), yo.contiguous()
+
+
 def inverse_code(code: int) -> int:
     """The code that undoes `code` (the two quarter turns swap; every other code is an involution)."""
     if code & T and bool(code & FH) != bool(code & FW):
@@ -252,16 +366,26 @@ def tta_mean_torch(predict_fn, x, codes):
 
 def make_aug(cfg, step: int) -> Optional[Callable[[Sequence[int]], Tuple[np.ndarray, Optional[np.ndarray]]]]:
     """The per-step callable a DeviceFeeder takes (dataset sample indices -> parameters),
-    or None when --augment is off."""
+    or None when --augment is off.  With `rotate` or `scale` named the parameters gain the warp
+    matrices as a last item: (code, affine, mat)."""
     names = parse_augment(cfg.augment)
     if not names:
         return None
-    return lambda idx: draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity)
+    if not has_spatial(names):
+        return lambda idx: draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity)
+    return lambda idx: draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity) + (
+        draw_spatial(cfg.seed, step, idx, names, cfg.augment_rotate, cfg.augment_scale),)
+
+
+def has_spatial(names) -> bool:
+    """Whether the --augment names hold a transform that resamples the image (rotate, scale)."""
+    return any(t in SPATIAL_NAMES for t in names)
 
 
 def make_crop_aug(cfg, step: int, stored, table=None):
     """make_aug's sibling for --crop: dataset sample indices -> (code, affine, origin).  The
-    codes are all zero and the affine None when --augment is off; the origins are draw_crop's."""
+    codes are all zero and the affine None when --augment is off; the origins are draw_crop's.
+    With `rotate` or `scale` named: (code, affine, origin, mat)."""
     mode, p_fg = parse_crop(cfg.crop)
     names = parse_augment(cfg.augment)
     patch = (cfg.img_size,) * 3 if cfg.dims == 3 else (1, cfg.img_size, cfg.img_size)
@@ -269,6 +393,9 @@ def make_crop_aug(cfg, step: int, stored, table=None):
     def fn(idx):
         code, affine = draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity)
         origin, _ = draw_crop(cfg.seed, step, idx, stored, patch, mode, p_fg, table)
+        if has_spatial(names):
+            return code, affine, origin, draw_spatial(cfg.seed, step, idx, names, cfg.augment_rotate,
+                                                      cfg.augment_scale)
         return code, affine, origin
 
     return fn

@@ -11,7 +11,7 @@ for sequential reads.  ``--num_threads`` (README.md:63) sizes the gather pool.
 import numpy as np
 import torch
 
-from .augment import apply_torch, crop_torch
+from .augment import apply_torch, crop_torch, warp_torch
 
 
 class BatchLoader:
@@ -72,7 +72,9 @@ class ResidentBatch:
     for the tensors.  `aug`: optional augmentation parameters of the batch on the
     device, (code int32 [n], affine float32 [n][Cin][2] or None) (data/augment.py).  `crop`:
     optional (origin int32 [n][3] on the device, patch dims (D, H, W)): the batch is the patch
-    of each stored sample at its origin (--crop), cropped before it is augmented."""
+    of each stored sample at its origin (--crop), cropped before it is augmented.  An `aug` of three
+    items ends in the warp matrices (mat int32 [n][4], --augment rotate / scale): the patch, or the
+    whole sample without `crop`, is resampled through them straight from the stored sample."""
 
     def __init__(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, aug=None, crop=None):
         self.x_all, self.y_all, self.idx = x_all, y_all, idx
@@ -81,6 +83,8 @@ class ResidentBatch:
 
     def tensors(self):
         x, y = self.x_all.index_select(0, self.idx), self.y_all.index_select(0, self.idx)
+        if self.aug is not None and len(self.aug) > 2 and self.aug[2] is not None:
+            return warp_batch(x, y, self.crop, *self.aug)
         if self.crop is not None:
             x, y = crop_torch(x, y, *self.crop)
         if self.aug is not None:
@@ -93,6 +97,15 @@ class ResidentBatch:
             d, h, w = self.crop[1]
             return int(self.idx.numel()) * d * h * w * int(self.y_all.shape[-1])
         return int(self.idx.numel()) * int(self.y_all[0].numel())
+
+
+def warp_batch(x, y, crop, code, affine, mat):
+    """The training transform with warp matrices on the samples x [n, (Ds,) Hs, Ws, C] and y of a
+    batch: `crop` = (origin [n][3], patch dims) or None (the whole sample at origin 0), then
+    warp_torch, then apply_torch(code or the identity, affine)."""
+    origin, patch = crop if crop is not None else (None, tuple(x.shape[1:-1]))
+    x, y = warp_torch(x, y, origin, patch, mat)
+    return apply_torch(x, y, code if code is not None else np.zeros(x.shape[0], dtype=np.int32), affine)
 
 
 class DeviceFeeder:
@@ -133,24 +146,30 @@ class DeviceFeeder:
         self.events = [None] * len(self.loaders)
         self.k = 0
 
-    def _upload(self, sorted_idx: np.ndarray, code: np.ndarray, affine, origin=None):
+    def _upload(self, sorted_idx: np.ndarray, code: np.ndarray, affine, origin=None, mat=None):
         """Index tensor and augmentation parameters in one small non-blocking copy:
-        [idx int64 | affine fp32 | code int32 | origin int32] -> (idx, (code, affine)) device
-        views, and with `origin` (int [n][3], --crop) the origin view as a third item."""
+        [idx int64 | affine fp32 | code int32 | origin int32 | mat int32] -> (idx, (code, affine))
+        device views, and with `origin` (int [n][3], --crop) the origin view as a third item.
+        With `mat` (int [n][4], --augment rotate / scale) the second item is (code, affine, mat)."""
         n = len(sorted_idx)
         af = np.ascontiguousarray(affine, dtype=np.float32) if affine is not None else np.empty(0, np.float32)
         parts = [sorted_idx.view(np.uint8), af.reshape(-1).view(np.uint8),
                  np.ascontiguousarray(code, dtype=np.int32).view(np.uint8)]
         if origin is not None:
             parts.append(np.ascontiguousarray(origin, dtype=np.int32).reshape(-1).view(np.uint8))
+        if mat is not None:
+            parts.append(np.ascontiguousarray(mat, dtype=np.int32).reshape(-1).view(np.uint8))
         buf = torch.from_numpy(np.concatenate(parts)).to(self.device, non_blocking=True)
         na = parts[1].size
         ii = buf[:8 * n].view(torch.int64)
         af = buf[8 * n:8 * n + na].view(torch.float32).view(affine.shape) if affine is not None else None
         cd = buf[8 * n + na:8 * n + na + 4 * n].view(torch.int32)
+        at = 8 * n + na + 4 * n
+        no = 12 * n if origin is not None else 0
+        dev = (cd, af) if mat is None else (cd, af, buf[at + no:at + no + 16 * n].view(torch.int32).view(n, 4))
         if origin is None:
-            return ii, (cd, af)
-        return ii, (cd, af), buf[8 * n + na + 4 * n:].view(torch.int32).view(n, 3)
+            return ii, dev
+        return ii, dev, buf[at:at + no].view(torch.int32).view(n, 3)
 
     def get(self, idx: np.ndarray, lazy: bool = False, aug=None):
         """(x, y) of the samples `idx`; lazy (resident data only): a ResidentBatch
@@ -158,7 +177,10 @@ class DeviceFeeder:
         sample indices -> (code, affine) (data/augment.py): the batch is augmented with
         them (a ResidentBatch carries them for the backend's gather kernel).  A feeder with
         `patch` needs `aug` to return (code, affine, origin) (augment.make_crop_aug): the batch
-        is the patches at the origins, cropped first and then augmented."""
+        is the patches at the origins, cropped first and then augmented.  Either tuple may end in
+        the warp matrices `mat` (--augment rotate / scale): the batch is then resampled through
+        them straight from the stored samples (augment.warp_torch; the backend's gather kernel
+        for a ResidentBatch)."""
         if aug is None:
             if self.patch is not None:
                 raise ValueError("a cropping feeder needs the per-step origins (aug)")
@@ -167,22 +189,34 @@ class DeviceFeeder:
         drawn = aug(si)
         if self.patch is not None:
             return self._get_crop(si, lazy, *drawn)
-        code, affine = drawn
+        code, affine, mat = drawn if len(drawn) > 2 else tuple(drawn) + (None,)
         if self.resident:
-            ii, dev = self._upload(si, code, affine)
+            ii, dev = self._upload(si, code, affine, mat=mat)
             if lazy:
                 return ResidentBatch(self.x, self.y, ii, dev), None
-            return apply_torch(self.x.index_select(0, ii), self.y.index_select(0, ii), code, affine)
-        return apply_torch(*self._get(idx, False), code, affine)
+            x, y = self.x.index_select(0, ii), self.y.index_select(0, ii)
+            return apply_torch(x, y, code, affine) if mat is None else warp_batch(x, y, None, code, affine, mat)
+        x, y = self._get(idx, False)
+        return apply_torch(x, y, code, affine) if mat is None else warp_batch(x, y, None, code, affine, mat)
 
-    def _get_crop(self, si: np.ndarray, lazy: bool, code, affine, origin):
+    def _get_crop(self, si: np.ndarray, lazy: bool, code, affine, origin, mat=None):
         origin = np.ascontiguousarray(origin, dtype=np.int32).reshape(len(si), 3)
         if self.resident:
-            ii, dev, org = self._upload(si, code, affine, origin)
+            ii, dev, org = self._upload(si, code, affine, origin, mat)
             if lazy:
                 return ResidentBatch(self.x, self.y, ii, dev, (org, self.patch)), None
-            x, y = crop_torch(self.x.index_select(0, ii), self.y.index_select(0, ii), origin, self.patch)
-            return apply_torch(x, y, code, affine)
+            x, y = self.x.index_select(0, ii), self.y.index_select(0, ii)
+            if mat is not None:
+                return warp_batch(x, y, (origin, self.patch), code, affine, mat)
+            return apply_torch(*crop_torch(x, y, origin, self.patch), code, affine)
+        if mat is not None:
+            # streamed and warped: the taps leave the patch rectangle, so the host resamples the
+            # whole stored samples and only the patches are copied to the device
+            ld = self.loaders[0]
+            x = torch.from_numpy(np.ascontiguousarray(ld.x[si], dtype=np.float32))
+            y = torch.from_numpy(np.ascontiguousarray(ld.y[si], dtype=np.float32))
+            x, y = warp_batch(x, y, (origin, self.patch), code, affine, mat)
+            return x.to(self.device), y.to(self.device)
         # streamed: the host copies each sample's patch into the patch-sized staging buffers
         return apply_torch(*self._get(si, False, origin), code, affine)
 

@@ -34,9 +34,9 @@ import torch
 
 from .. import native
 from ..models.spec import UNetSpec
-from .native_engine import (gather_aug_args, gather_crop_args, plan_case_stats, plan_case_surface, plan_components,
-                            plan_tta, run_case_stats, run_case_surface, run_components, run_evaluate_tta,
-                            run_predict_sliding)
+from .native_engine import (gather_aug_args, gather_crop_args, gather_warp_args, has_mat, plan_case_stats,
+                            plan_case_surface, plan_components, plan_tta, run_case_stats, run_case_surface,
+                            run_components, run_evaluate_tta, run_predict_sliding)
 from .params import FlatParams
 from .plan_check import RecordingPlan
 
@@ -398,7 +398,19 @@ class NativeUNetF32:
         f32_gather_batch_aug launch gathers and transforms the batch (kernels/gather_aug.h).
         `crop`: optional (origin int32 [B][3] on the device, patch dims): one
         f32_gather_batch_crop launch reads each sample's patch of the larger stored samples and
-        transforms it (kernels/gather_crop.h)."""
+        transforms it (kernels/gather_crop.h).  An `aug` of three items ends in the warp
+        matrices (mat int32 [B][4]): one f32_gather_batch_warp launch resamples the patch, or the
+        whole sample without `crop`, through them (kernels/gather_warp.h)."""
+        if has_mat(aug):
+            cin = self.spec.in_channels
+            K = y_all[0].numel() * cin // x_all[0].numel()
+            assert idx.dtype == torch.int64 and idx.numel() == self.B and x_all.dtype == torch.float32
+            assert y_all.dtype == torch.float32 and x_all.is_contiguous() and y_all.is_contiguous()
+            assert self.target.numel() == self.npix(1) * K and self.bufs["x"].numel() == self.npix(1) * cin
+            ptrs, ints = gather_warp_args(self, x_all, y_all, idx, aug, crop, cin, cin, K)
+            self.C.generic("f32_gather_batch_warp", ptrs, ints, [], native.stream_handle(stream), 0)
+            return
+        aug = aug[:2] if aug is not None else None
         if crop is not None:
             cin = self.spec.in_channels
             K = y_all[0].numel() * cin // x_all[0].numel()

@@ -2016,11 +2016,19 @@ class NativeUNet:
         (data/augment.py): the same launch flips / rotates each sample and applies its
         per-channel affine (kernels/gather_aug.h).  `crop`: optional (origin int32 [B][3] on
         the device, patch dims): the stored samples are larger than the model's input and the
-        launch reads each sample's patch at its origin, then transforms it (kernels/gather_crop.h)."""
+        launch reads each sample's patch at its origin, then transforms it (kernels/gather_crop.h).
+        An `aug` of three items (code or None, affine or None, mat int32 [B][4]) resamples the
+        patch -- the whole sample without `crop` -- through each sample's matrix in the same
+        launch (kernels/gather_warp.h)."""
         cin = self.spec.in_channels
         P = x_all[0].numel() // cin
         assert idx.dtype == torch.int64 and idx.numel() == self.B and x_all.dtype == torch.float32
         assert y_all[0].numel() == P * self.K and x_all.is_contiguous() and y_all.is_contiguous()
+        if has_mat(aug):
+            ptrs, ints = gather_warp_args(self, x_all, y_all, idx, aug, crop, cin, self.cpad, self.K)
+            self.C.generic("gather_batch_warp", ptrs, ints, [], native.stream_handle(stream), self.dt_id)
+            return
+        aug = aug[:2] if aug is not None else None
         if crop is not None:
             ptrs, ints = gather_crop_args(self, x_all, y_all, idx, aug, crop, cin, self.cpad, self.K)
             self.C.generic("gather_batch_crop", ptrs, ints, [], native.stream_handle(stream), self.dt_id)
@@ -2257,6 +2265,44 @@ def gather_crop_args(e, x_all, y_all, idx, aug, crop, cin: int, cpad: int, K: in
                          % (e.B, cin, x_all.device))
     ptrs = [_ptr(x_all), _ptr(y_all), _ptr(idx), _ptr(origin), _ptr(code) if code is not None else 0,
             _ptr(affine) if affine is not None else 0, _ptr(e.bufs["x"]), _ptr(e.target)]
+    return ptrs, [e.B, Ds, Hs, Ws, patch[0], patch[1], patch[2], cin, cpad, K]
+
+
+def has_mat(aug) -> bool:
+    """Whether the augmentation parameters `aug` end in warp matrices: (code, affine, mat)."""
+    return aug is not None and len(aug) > 2 and aug[2] is not None
+
+
+def gather_warp_args(e, x_all, y_all, idx, aug, crop, cin: int, cpad: int, K: int):
+    """(ptrs, ints) of an executor's gather_batch_warp / f32_gather_batch_warp launch
+    (bindings.cpp) from the resident dataset [N, (Ds,) Hs, Ws, Cin], `aug` = (code or None,
+    affine or None, mat int32 [B][4]) and `crop` = (origin int32 [B][3], patch dims (D, H, W)) or
+    None: the patch is then the executor's input at origin 0, which the stored sample must hold."""
+    code, affine, mat = aug
+    Ds = x_all.shape[1] if x_all.dim() == 5 else 1
+    Hs, Ws = x_all.shape[-3], x_all.shape[-2]
+    origin, patch = crop if crop is not None else (None, e.sdims(1))
+    patch = tuple(int(v) for v in patch)
+    if patch != tuple(e.sdims(1)):
+        raise ValueError("crop patch %r: the executor's input is %r" % (patch, tuple(e.sdims(1))))
+    if any(t > s for t, s in zip(patch, (Ds, Hs, Ws))):
+        raise ValueError("the executor's input %r exceeds the stored sample %r" % (patch, (Ds, Hs, Ws)))
+    if (mat.dtype != torch.int32 or tuple(mat.shape) != (e.B, 4) or mat.device != x_all.device
+            or not mat.is_contiguous()):
+        raise ValueError("warp matrices: a contiguous int32 [%d][4] tensor on %s" % (e.B, x_all.device))
+    if origin is not None and (origin.dtype != torch.int32 or tuple(origin.shape) != (e.B, 3)
+                               or origin.device != x_all.device or not origin.is_contiguous()):
+        raise ValueError("crop origins: a contiguous int32 [%d][3] tensor on %s" % (e.B, x_all.device))
+    if code is not None and (code.dtype != torch.int32 or code.numel() != e.B or code.device != x_all.device
+                             or not code.is_contiguous()):
+        raise ValueError("augmentation codes: a contiguous int32 [%d] tensor on %s" % (e.B, x_all.device))
+    if affine is not None and (affine.dtype != torch.float32 or tuple(affine.shape) != (e.B, cin, 2)
+                               or affine.device != x_all.device or not affine.is_contiguous()):
+        raise ValueError("augmentation affine: a contiguous float32 [%d][%d][2] tensor on %s"
+                         % (e.B, cin, x_all.device))
+    ptrs = [_ptr(x_all), _ptr(y_all), _ptr(idx), _ptr(origin) if origin is not None else 0,
+            _ptr(code) if code is not None else 0, _ptr(mat), _ptr(affine) if affine is not None else 0,
+            _ptr(e.bufs["x"]), _ptr(e.target)]
     return ptrs, [e.B, Ds, Hs, Ws, patch[0], patch[1], patch[2], cin, cpad, K]
 
 
