@@ -44,7 +44,6 @@ def workload(dims, B, K, N, img, once):
     from unet_distributed_amd.models import reference
     from unet_distributed_amd.models.spec import spec_from_config
     from unet_distributed_amd.runtime.backends import NativeBackend
-    from unet_distributed_amd.runtime.native_engine import plan_sliding
     from unet_distributed_amd.runtime.params import FlatParams
     cfg = Config(batch_size=B, dims=dims, img_size=128, in_channels=4, out_channels=K, hip_graph=False)
     spec = spec_from_config(cfg)
@@ -68,8 +67,8 @@ def workload(dims, B, K, N, img, once):
         torch.cuda.synchronize()
         print(json.dumps(rec), flush=True)
         return
-    plan_sliding(e)
-    acc = torch.zeros((N,) + d3 + (K,), device=dev)
+    e.plan_sliding()
+    acc =torch.zeros((N,) + d3 + (K,), device=dev)
     wsum = sliding.weight_sum(d3, T, stride, "gaussian").to(dev)
     st = int(torch.cuda.current_stream().cuda_stream)
     head, tail = [N] + list(d3), list(T) + list(stride) + [B, 0, B]

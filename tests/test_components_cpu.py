@@ -257,7 +257,7 @@ def test_components_plan_time_validation():
 
 
 def test_sample_groups_cover_the_batch_within_the_cap():
-    from unet_distributed_amd.runtime.native_engine import COMP_SCRATCH_CAP, components_group
+    from unet_distributed_amd.runtime.executor_base import COMP_SCRATCH_CAP, components_group
     C = _C()
     assert COMP_SCRATCH_CAP == 256 << 20
     assert components_group(C, 1024, 1, 128, 128, 1) == 1024            # 128 MiB: one group

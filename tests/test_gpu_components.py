@@ -151,7 +151,7 @@ def _case(shape, combo):
 def _launch(prob_d, shape, combo, fill=0xFF, group=None):
     """One op (or, with `group`, the grouped launches) into slices of guard-filled allocations,
     the scratch pre-filled with `fill` bytes; returns (out, info, guards intact, launches)."""
-    from unet_distributed_amd.runtime.native_engine import launch_components
+    from unet_distributed_amd.runtime.executor_base import launch_components
     K, thr, largest, min_size = combo
     N, D, H, W = shape
     dev = prob_d.device
@@ -232,7 +232,7 @@ def test_two_runs_give_the_same_bits_whatever_the_scratch_held(cuda_dev, shape):
 
 def test_sample_groups_give_the_one_group_result(cuda_dev):
     """Five samples in groups of two (a scratch sized for two): three launches, the same bits."""
-    from unet_distributed_amd.runtime.native_engine import components_group
+    from unet_distributed_amd.runtime.executor_base import components_group
     shape, combo = (5, 1, 16, 24), COMBOS[5]
     prob, want_out, want_info = _case(shape, combo)
     prob_d = prob.to(cuda_dev)

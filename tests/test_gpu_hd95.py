@@ -181,7 +181,7 @@ def test_two_runs_give_the_same_bits_whatever_the_scratch_held(cuda_dev, shape):
 
 def test_sample_groups_through_a_small_scratch(cuda_dev):
     """Five samples through a scratch sized for two: three launches, the one-group result."""
-    from unet_distributed_amd.runtime.native_engine import launch_surf_dist
+    from unet_distributed_amd.runtime.executor_base import launch_surf_dist
     shape, K = (5, 1, 16, 24), 2
     N, D, H, W = shape
     prob, tgt, want, thr = _case(shape, K)

@@ -199,7 +199,7 @@ def test_surf_dist_plan_time_validation(kind):
 
 
 def test_sample_groups_cover_the_batch_within_the_scratch():
-    from unet_distributed_amd.runtime.native_engine import SURF_SCRATCH_CAP, surf_dist_group
+    from unet_distributed_amd.runtime.executor_base import SURF_SCRATCH_CAP, surf_dist_group
     C = _C()
     assert SURF_SCRATCH_CAP == 256 << 20
     one = C.surf_dist_scratch(1, 1, 128, 128, 4)

@@ -304,7 +304,6 @@ def _dry_engine(cfg, **kw):
 @pytest.mark.parametrize("kw", ENGINES, ids=lambda kw: "-".join("%s" % v for v in kw.values()))
 def test_dry_run_engines_expose_sliding_to_plan_check(kw):
     from unet_distributed_amd.config import Config
-    from unet_distributed_amd.runtime.native_engine import plan_sliding
     from unet_distributed_amd.runtime.plan_check import check_engine, check_sliding_plan
     cfg = Config(**kw)
     e = _dry_engine(cfg)
@@ -312,7 +311,7 @@ def test_dry_run_engines_expose_sliding_to_plan_check(kw):
     assert e.sw_plan is None and not hasattr(e, "sw_x")
     assert check_sliding_plan(e) != []
     names = (e.plan.names(), e.eval_plan.names())
-    plan_sliding(e)
+    e.plan_sliding()
     B = cfg.batch_size
     want = ["sw_extract:0", "sw_blend:0", "sw_finish"] if B >= 2 else \
         ["sw_extract:0", "sw_blend:0", "sw_extract:1", "sw_blend:1", "sw_finish"]

@@ -392,7 +392,7 @@ class NativeBackend:
     @torch.no_grad()
     def predict_sliding(self, x, overlap: float = 0.5, blend: str = "gaussian", post: bool = True) -> torch.Tensor:
         """Probabilities fp32 [n, (D,) H, W, K] of images of any spatial size, on the device: the
-        executor's sliding-window path (`native_engine.run_predict_sliding`: sw_extract, the
+        executor's sliding-window path (`ExecutorBase.predict_sliding`: sw_extract, the
         evaluation forward -- with --eval_tta the mean over the transforms -- and sw_blend per
         batch of tiles, then sw_finish).  The executor's buffer, overwritten by the next call.
         post=False: the blended map itself, before the --eval_components filter."""
@@ -402,15 +402,15 @@ class NativeBackend:
 
     def _sw_filter(self, p, threshold: float):
         """(p, None) with the filter off, else (filtered p, info) of a full-size map
-        (`native_engine.sliding_components`); the last result is kept and a map that is itself
+        (`executor_base.sliding_components`); the last result is kept and a map that is itself
         that result is not filtered again."""
         if self.components is None:
             return p, None
         c = self._sw_pp
         if c is not None and c[1] == threshold and c[2] is p:
             return c[2], c[3]
-        from .native_engine import sliding_components
-        out, info = sliding_components(self.engine, p, threshold, *self.components)
+        from .executor_base import sliding_components
+        out, info = sliding_components(self.engine.C, p, threshold, *self.components)
         self._sw_pp = (None, threshold, out, info)
         return out, info
 
@@ -430,14 +430,14 @@ class NativeBackend:
     def sliding_stats(self, p, y, threshold: float = 0.5, post: bool = True) -> torch.Tensor:
         """fp32 [n][K][6] of full-size probabilities p (`predict_sliding`) against the target y.
         post=False: of p itself, the --eval_components filter not applied."""
-        from .native_engine import sliding_stats
-        return sliding_stats(self.engine, self._sw_filter(p, threshold)[0] if post else p, y, threshold)
+        from .executor_base import sliding_stats
+        return sliding_stats(self.engine.C, self._sw_filter(p, threshold)[0] if post else p, y, threshold)
 
     @torch.no_grad()
     def sliding_surface(self, p, y, threshold: float = 0.5) -> torch.Tensor:
         """int32 [n][K][4] of full-size probabilities p (`predict_sliding`) against the target y."""
-        from .native_engine import sliding_surface
-        return sliding_surface(self.engine, self._sw_filter(p, threshold)[0], y, threshold)
+        from .executor_base import sliding_surface
+        return sliding_surface(self.engine.C, self._sw_filter(p, threshold)[0], y, threshold)
 
     def adam_step(self, lr, b1p, b2p, grad_scale=1.0):
         self.engine.adam_step(lr, b1p, b2p, grad_scale)

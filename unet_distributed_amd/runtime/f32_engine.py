@@ -34,20 +34,15 @@ import torch
 
 from .. import native
 from ..models.spec import UNetSpec
-from .native_engine import (gather_aug_args, gather_crop_args, gather_warp_args, has_mat, plan_case_stats,
-                            plan_case_surface, plan_components, plan_tta, run_case_stats, run_case_surface,
-                            run_components, run_evaluate_tta, run_predict_sliding)
+from .executor_base import ExecutorBase, _ptr
 from .params import FlatParams
 from .plan_check import RecordingPlan
 
 
-def _ptr(t: Optional[torch.Tensor]) -> int:
-    return 0 if t is None else int(t.data_ptr())
-
-
-class NativeUNetF32:
+class NativeUNetF32(ExecutorBase):
     """Plans and runs forward + backward of one fp32 UNet micro-batch on the GPU."""
 
+    OP_PREFIX = "f32_"
     WG_SPLIT_TARGET = 256           # split-K slabs per weight gradient (~1 workgroup per CU and tile)
 
     def __init__(self, spec: UNetSpec, flat: FlatParams, batch: int, img: int, device, loss: str = "dice",
@@ -70,6 +65,8 @@ class NativeUNetF32:
         self.loss = loss
         self.bce_weight = float(bce_weight) if loss == "dice_bce" else 0.0
         self.dtype = "fp32"
+        # one class, no 16-bit type, the input buffer unpadded (the interface of ExecutorBase)
+        self.K, self.dt_id, self.cpad = 1, 0, spec.in_channels
         self.state: Dict[str, torch.Tensor] = {}
         self.fusions: Dict[str, List[str]] = {}
         self.graphs = None
@@ -84,28 +81,10 @@ class NativeUNetF32:
         self.bwd_end = self.plan.size()
         self._build_forward(self.eval_plan, dropout=eval_dropout)
         self.set_buckets(bucket_bounds)
-        plan_case_stats(self, "f32_seg_stats")
-        self.surface_plan = self.case_surface_buf = self.case_surface_scratch = None
-        if eval_hd95:            # (otherwise on the first case_surface call)
-            plan_case_surface(self, "f32_surf_dist")
-        self.tta_plan = self.tta_acc_buf = self.tta_partial = None
-        if eval_tta:             # (otherwise on the first evaluate_tta call)
-            plan_tta(self, "f32_tta_finish")
-        self.sw_plan = None      # (sliding-window inference: on the first predict_sliding call, or plan_sliding)
-        self.components_plan = self.prob_pp = self.components_info = self.components_scratch = None
-        if eval_components:      # (otherwise on the first components call)
-            plan_components(self)
+        self._init_eval_ops(eval_hd95, eval_tta, eval_components)
         self._adam_segs()
 
-    # ------------------------------------------------------------------ shapes / buffers
-    def sdims(self, level: int):
-        s = self.img >> (level - 1)
-        return (s, s, s) if self.dims == 3 else (1, s, s)
-
-    def npix(self, level: int) -> int:
-        d, h, w = self.sdims(level)
-        return self.B * d * h * w
-
+    # ------------------------------------------------------------------ buffers
     def _buf(self, name, level, ch):
         d, h, w = self.sdims(level)
         shape = (self.B, h, w, ch) if self.dims == 2 else (self.B, d, h, w, ch)
@@ -319,14 +298,15 @@ class NativeUNetF32:
                         lvl = self.tinfo[src1][0]
                         dd, hh, ww = self.sdims(lvl)
                         mk, _ = self._mask_of(src1)
-                        plan.add_generic("f32_ups_bwd", [_ptr(b["dfull:" + src1]), _ptr(mk), _ptr(b["d:" + src1])],
+                        plan.add_generic("f32_ups_bwd", [_ptr(b["dfull:" + src1]), _ptr(mk) or 0, _ptr(b["d:" + src1])],
                                          [self.B, dd, hh, ww, c1, int(self.dims == 3)], [], "bwd:up:" + src1)
                 self._layer_done_at[l.name] = plan.size()
             elif l.kind == "pool":
                 src = self.inputs[l.name][0]
                 dd, hh, ww = self.sdims(l.level)
                 sk = b.get("dskip:" + src)
-                plan.add_generic("f32_pool_bwd", [_ptr(b[src]), _ptr(b["d:" + l.name]), _ptr(sk), _ptr(b["d:" + src])],
+                plan.add_generic("f32_pool_bwd",
+                                 [_ptr(b[src]), _ptr(b["d:" + l.name]), _ptr(sk) or 0, _ptr(b["d:" + src])],
                                  [self.B, dd, hh, ww, l.cout, int(self.dims == 3)], [], "bwd:" + l.name)
             elif l.kind == "tconv":
                 src = self.inputs[l.name][0]
@@ -393,43 +373,8 @@ class NativeUNetF32:
         self.bufs["x"].view(-1).copy_(x.reshape(-1), non_blocking=True)
         self.target.copy_(y.reshape(-1), non_blocking=True)
 
-    def load_indexed(self, x_all, y_all, idx, stream=None, aug=None, crop=None):
-        """`aug`: optional (code, affine) on the device (data/augment.py): one
-        f32_gather_batch_aug launch gathers and transforms the batch (kernels/gather_aug.h).
-        `crop`: optional (origin int32 [B][3] on the device, patch dims): one
-        f32_gather_batch_crop launch reads each sample's patch of the larger stored samples and
-        transforms it (kernels/gather_crop.h).  An `aug` of three items ends in the warp
-        matrices (mat int32 [B][4]): one f32_gather_batch_warp launch resamples the patch, or the
-        whole sample without `crop`, through them (kernels/gather_warp.h)."""
-        if has_mat(aug):
-            cin = self.spec.in_channels
-            K = y_all[0].numel() * cin // x_all[0].numel()
-            assert idx.dtype == torch.int64 and idx.numel() == self.B and x_all.dtype == torch.float32
-            assert y_all.dtype == torch.float32 and x_all.is_contiguous() and y_all.is_contiguous()
-            assert self.target.numel() == self.npix(1) * K and self.bufs["x"].numel() == self.npix(1) * cin
-            ptrs, ints = gather_warp_args(self, x_all, y_all, idx, aug, crop, cin, cin, K)
-            self.C.generic("f32_gather_batch_warp", ptrs, ints, [], native.stream_handle(stream), 0)
-            return
-        aug = aug[:2] if aug is not None else None
-        if crop is not None:
-            cin = self.spec.in_channels
-            K = y_all[0].numel() * cin // x_all[0].numel()
-            assert idx.dtype == torch.int64 and idx.numel() == self.B and x_all.dtype == torch.float32
-            assert y_all.dtype == torch.float32 and x_all.is_contiguous() and y_all.is_contiguous()
-            assert self.target.numel() == self.npix(1) * K and self.bufs["x"].numel() == self.npix(1) * cin
-            ptrs, ints = gather_crop_args(self, x_all, y_all, idx, aug, crop, cin, cin, K)
-            self.C.generic("f32_gather_batch_crop", ptrs, ints, [], native.stream_handle(stream), 0)
-            return
-        if aug is not None:
-            cin = self.spec.in_channels
-            K = y_all[0].numel() * cin // x_all[0].numel()
-            assert idx.dtype == torch.int64 and idx.numel() == self.B and x_all.dtype == torch.float32
-            assert y_all.dtype == torch.float32 and x_all.is_contiguous() and y_all.is_contiguous()
-            assert self.bufs["x"].numel() == self.B * x_all[0].numel()
-            assert self.target.numel() == self.B * y_all[0].numel()
-            ptrs, ints = gather_aug_args(self, x_all, y_all, idx, aug, cin, cin, K)
-            self.C.generic("f32_gather_batch_aug", ptrs, ints, [], native.stream_handle(stream), 0)
-            return
+    def _load_plain(self, x_all, y_all, idx, stream):
+        """(no fp32 gather_batch kernel: an index_select and a copy)"""
         self.bufs["x"].copy_(x_all.index_select(0, idx).view_as(self.bufs["x"]))
         self.target.copy_(y_all.index_select(0, idx).reshape(-1))
 
@@ -452,48 +397,3 @@ class NativeUNetF32:
             begin = max(begin, end)
             if on_segment is not None:
                 on_segment(i)
-
-    def evaluate_batch(self, stream=None):
-        self._live()
-        self.eval_plan.set_seed(0)
-        self.eval_plan.run(0, self.eval_plan.size(), native.stream_handle(stream))
-
-    def probs(self) -> torch.Tensor:
-        d, h, w = self.sdims(1)
-        shape = (self.B, h, w, 1) if self.dims == 2 else (self.B, d, h, w, 1)
-        return self.prob.view(shape)
-
-    def case_stats(self, threshold: float = 0.5, stream=None, post: bool = False) -> torch.Tensor:
-        """[B][1][6] = {I, St, Sp, TP, FP, FN} per sample of the probabilities and the fp32
-        target the last forward / evaluate_batch left behind (one launch, seg_stats.h);
-        `post`: of the filtered probabilities `prob_pp` of the last `components` call."""
-        return run_case_stats(self, "f32_seg_stats", threshold, stream, post)
-
-    def case_surface(self, threshold: float = 0.5, stream=None, post: bool = False) -> torch.Tensor:
-        """int32 [B][1][4] = {mp, mt, q_lo, q_hi} per sample of the probabilities and the fp32
-        target the last forward / evaluate_batch left behind (surf_dist.h); `post`: of the
-        filtered probabilities `prob_pp` of the last `components` call."""
-        return run_case_surface(self, "f32_surf_dist", threshold, stream, post)
-
-    def components(self, threshold: float = 0.5, keep_largest: bool = True, min_size: int = 0,
-                   stream=None) -> torch.Tensor:
-        """Connected-component filter (components.h) of the probabilities the last forward /
-        evaluate_batch left behind: `prob_pp` holds the filtered map; returns the int32
-        [B][1][4] = {components, kept components, largest size, kept voxels} buffer."""
-        return run_components(self, threshold, keep_largest, min_size, stream)
-
-    def probs_pp(self) -> torch.Tensor:
-        """`prob_pp` in the shape of `probs()` (after a `components` call)."""
-        return self.prob_pp.view(self.probs().shape)
-
-    def evaluate_tta(self, x: torch.Tensor, y: torch.Tensor, codes, stream=None):
-        """Test-time augmentation of the batch (x, y) over the transform codes `codes`
-        (`data.augment.tta_codes`): `prob` then holds the mean, `target` the stored target and
-        `sums` the sums of that mean (tta.h, `native_engine.run_evaluate_tta`)."""
-        return run_evaluate_tta(self, x, y, codes, stream)
-
-    def predict_sliding(self, x: torch.Tensor, overlap: float = 0.5, blend: str = "gaussian", tta_codes=(),
-                        stream=None) -> torch.Tensor:
-        """Sliding-window probabilities fp32 [N, (D,) H, W, 1] of device images of any spatial
-        size (`native_engine.run_predict_sliding`, kernels/sliding.h): the executor's buffer."""
-        return run_predict_sliding(self, x, overlap, blend, tta_codes, stream)

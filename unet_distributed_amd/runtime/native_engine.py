@@ -37,13 +37,9 @@ import torch
 
 from .. import native
 from ..models.spec import UNetSpec
+from .executor_base import ExecutorBase, _ptr
 from .params import FlatParams
 from .plan_check import RecordingPlan
-
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else int(t.data_ptr())
 
 
 def _r64(k: int) -> int:
@@ -211,7 +207,7 @@ def engine_options(overrides: Optional[Dict[str, int]] = None) -> Dict[str, int]
     return opts
 
 
-class NativeUNet:
+class NativeUNet(ExecutorBase):
     """Plans and runs forward + backward of one UNet micro-batch on the GPU."""
 
     def __init__(self, spec: UNetSpec, flat: FlatParams, batch: int, img: int,
@@ -294,17 +290,7 @@ class NativeUNet:
         self.bwd_end = self.plan.size()
         self._build_forward(self.eval_plan, dropout=eval_dropout, train=False)
         self.set_buckets(bucket_bounds)
-        plan_case_stats(self, "seg_stats")
-        self.surface_plan = self.case_surface_buf = self.case_surface_scratch = None
-        if eval_hd95:            # (otherwise on the first case_surface call: the default trainer does not grow)
-            plan_case_surface(self, "surf_dist")
-        self.tta_plan = self.tta_acc_buf = self.tta_partial = None
-        if eval_tta:             # (otherwise on the first evaluate_tta call)
-            plan_tta(self, "tta_finish")
-        self.sw_plan = None      # (sliding-window inference: on the first predict_sliding call, or plan_sliding)
-        self.components_plan = self.prob_pp = self.components_info = self.components_scratch = None
-        if eval_components:      # (otherwise on the first components call)
-            plan_components(self)
+        self._init_eval_ops(eval_hd95, eval_tta, eval_components)
         if not dry_run:          # dry_run: plan construction only (CPU tests, no GPU launches)
             self.repack()
 
@@ -331,15 +317,7 @@ class NativeUNet:
         if layer not in self.fusions[name]:
             self.fusions[name].append(layer)
 
-    # ------------------------------------------------------------------ shapes
-    def sdims(self, level: int) -> Tuple[int, int, int]:
-        s = self.img >> (level - 1)
-        return (s, s, s) if self.dims == 3 else (1, s, s)
-
-    def npix(self, level: int) -> int:
-        d, h, w = self.sdims(level)
-        return self.B * d * h * w
-
+    # ------------------------------------------------------------------ buffers
     def _buf(self, name, level, ch, dtype=None):
         dtype = self.adt if dtype is None else dtype
         d, h, w = self.sdims(level)
@@ -1998,9 +1976,7 @@ class NativeUNet:
         if (x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and x.is_contiguous()
                 and y.is_contiguous() and x.shape[0] == self.B and y.numel() * cin == x.numel() * self.K):
             # one launch: cast into the channel-padded 16-bit input and the target
-            if getattr(self, "_iota", None) is None:
-                self._iota = torch.arange(self.B, device=self.device, dtype=torch.int64)
-            return self.load_indexed(x, y, self._iota, stream)
+            return self.load_indexed(x, y, self._batch_iota(), stream)
         xb = self.bufs["x"].view(-1, self.cpad)
         (xb if cin == self.cpad else xb[:, :cin]).copy_(x.reshape(-1, cin), non_blocking=True)
         if y.numel() != self.target.numel():
@@ -2008,37 +1984,12 @@ class NativeUNet:
                              % (y.numel(), self.target.numel(), self.B, self.K))
         self.target.copy_(y.reshape(-1), non_blocking=True)
 
-    def load_indexed(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, stream=None, aug=None,
-                     crop=None):
-        """Batch = samples `idx` (device int64) of the HBM-resident dataset, gathered
-        and cast straight into the padded 16-bit input and target (one launch).  `aug`:
-        optional (code int32 [B], affine float32 [B][Cin][2] or None) on the device
-        (data/augment.py): the same launch flips / rotates each sample and applies its
-        per-channel affine (kernels/gather_aug.h).  `crop`: optional (origin int32 [B][3] on
-        the device, patch dims): the stored samples are larger than the model's input and the
-        launch reads each sample's patch at its origin, then transforms it (kernels/gather_crop.h).
-        An `aug` of three items (code or None, affine or None, mat int32 [B][4]) resamples the
-        patch -- the whole sample without `crop` -- through each sample's matrix in the same
-        launch (kernels/gather_warp.h)."""
+    def _load_plain(self, x_all, y_all, idx, stream):
+        """Gather and cast straight into the padded 16-bit input and target (one launch)."""
         cin = self.spec.in_channels
-        P = x_all[0].numel() // cin
-        assert idx.dtype == torch.int64 and idx.numel() == self.B and x_all.dtype == torch.float32
-        assert y_all[0].numel() == P * self.K and x_all.is_contiguous() and y_all.is_contiguous()
-        if has_mat(aug):
-            ptrs, ints = gather_warp_args(self, x_all, y_all, idx, aug, crop, cin, self.cpad, self.K)
-            self.C.generic("gather_batch_warp", ptrs, ints, [], native.stream_handle(stream), self.dt_id)
-            return
-        aug = aug[:2] if aug is not None else None
-        if crop is not None:
-            ptrs, ints = gather_crop_args(self, x_all, y_all, idx, aug, crop, cin, self.cpad, self.K)
-            self.C.generic("gather_batch_crop", ptrs, ints, [], native.stream_handle(stream), self.dt_id)
-            return
-        if aug is not None:
-            ptrs, ints = gather_aug_args(self, x_all, y_all, idx, aug, cin, self.cpad, self.K)
-            self.C.generic("gather_batch_aug", ptrs, ints, [], native.stream_handle(stream), self.dt_id)
-            return
+        self._check_indexed(x_all, y_all, idx)
         self.C.generic("gather_batch", [_ptr(x_all), _ptr(y_all), _ptr(idx), _ptr(self.bufs["x"]), _ptr(self.target)],
-                       [self.B, P, cin, self.cpad] + self._head_k(), [],
+                       [self.B, x_all[0].numel() // cin, cin, self.cpad] + self._head_k(), [],
                        native.stream_handle(stream), self.dt_id)
 
     # ------------------------------------------------------------------ HIP graphs
@@ -2173,548 +2124,3 @@ class NativeUNet:
             begin = end
             if on_segment is not None:
                 on_segment(i)
-
-    def evaluate_batch(self, stream=None):
-        """Inference forward (eval plan) of the loaded batch; sums -> self.sums."""
-        self.eval_plan.set_seed(0)
-        self.eval_plan.run(0, self.eval_plan.size(), native.stream_handle(stream))
-
-    def probs(self) -> torch.Tensor:
-        d, h, w = self.sdims(1)
-        shape = (self.B, h, w, self.K) if self.dims == 2 else (self.B, d, h, w, self.K)
-        return self.prob.view(shape)
-
-    def case_stats(self, threshold: float = 0.5, stream=None, post: bool = False) -> torch.Tensor:
-        """[B][K][6] = {I, St, Sp, TP, FP, FN} per (sample, class) of the probabilities and
-        target the last forward / evaluate_batch left behind (one launch; the returned
-        tensor is the executor's buffer, overwritten by the next call).  `post`: of the
-        filtered probabilities `prob_pp` the last `components` call left behind."""
-        return run_case_stats(self, "seg_stats", threshold, stream, post)
-
-    def case_surface(self, threshold: float = 0.5, stream=None, post: bool = False) -> torch.Tensor:
-        """int32 [B][K][4] = {mp, mt, q_lo, q_hi} per (sample, class): the surface sizes of
-        {prob >= threshold} and {target >= 0.5} and the two squared surface distances that
-        bracket the 95th percentile (`ops.seg_metrics.hd95_from_surface`), of the
-        probabilities and target the last forward / evaluate_batch left behind.  The
-        returned tensor is the executor's buffer, overwritten by the next call.  `post`: of
-        the filtered probabilities `prob_pp` the last `components` call left behind."""
-        return run_case_surface(self, "surf_dist", threshold, stream, post)
-
-    def components(self, threshold: float = 0.5, keep_largest: bool = True, min_size: int = 0,
-                   stream=None) -> torch.Tensor:
-        """Connected-component filter (kernels/components.h, `ops.components` is the
-        definition) of the probabilities the last forward / evaluate_batch left behind:
-        `prob_pp` (see `probs_pp`) holds the filtered map and the returned int32 [B][K][4] =
-        {components, kept components, largest size, kept voxels} is the executor's buffer."""
-        return run_components(self, threshold, keep_largest, min_size, stream)
-
-    def probs_pp(self) -> torch.Tensor:
-        """`prob_pp` in the shape of `probs()` (after a `components` call)."""
-        return self.prob_pp.view(self.probs().shape)
-
-    def evaluate_tta(self, x: torch.Tensor, y: torch.Tensor, codes, stream=None):
-        """Test-time augmentation of the batch (x, y) over the transform codes `codes`
-        (`data.augment.tta_codes`): afterwards `prob` holds the mean of the un-augmented
-        probabilities, `target` the stored target and `sums` the sums of that mean."""
-        return run_evaluate_tta(self, x, y, codes, stream)
-
-    def predict_sliding(self, x: torch.Tensor, overlap: float = 0.5, blend: str = "gaussian", tta_codes=(),
-                        stream=None) -> torch.Tensor:
-        """Sliding-window probabilities fp32 [N, (D,) H, W, K] of device images of any spatial
-        size (`run_predict_sliding`, kernels/sliding.h): the executor's buffer."""
-        return run_predict_sliding(self, x, overlap, blend, tta_codes, stream)
-
-
-def gather_aug_args(e, x_all, y_all, idx, aug, cin: int, cpad: int, K: int):
-    """(ptrs, ints) of an executor's gather_batch_aug / f32_gather_batch_aug launch
-    (bindings.cpp) from the resident dataset [N, (D,) H, W, Cin] and `aug` = (code, affine)."""
-    code, affine = aug
-    D = x_all.shape[1] if x_all.dim() == 5 else 1
-    H, W = x_all.shape[-3], x_all.shape[-2]
-    if code.dtype != torch.int32 or code.numel() != e.B or code.device != x_all.device or not code.is_contiguous():
-        raise ValueError("augmentation codes: a contiguous int32 [%d] tensor on %s" % (e.B, x_all.device))
-    if affine is not None and (affine.dtype != torch.float32 or tuple(affine.shape) != (e.B, cin, 2)
-                               or affine.device != x_all.device or not affine.is_contiguous()):
-        raise ValueError("augmentation affine: a contiguous float32 [%d][%d][2] tensor on %s"
-                         % (e.B, cin, x_all.device))
-    ptrs = [_ptr(x_all), _ptr(y_all), _ptr(idx), _ptr(code), _ptr(affine) if affine is not None else 0,
-            _ptr(e.bufs["x"]), _ptr(e.target)]
-    return ptrs, [e.B, D, H, W, cin, cpad, K]
-
-
-def gather_crop_args(e, x_all, y_all, idx, aug, crop, cin: int, cpad: int, K: int):
-    """(ptrs, ints) of an executor's gather_batch_crop / f32_gather_batch_crop launch
-    (bindings.cpp) from the resident dataset [N, (Ds,) Hs, Ws, Cin], `aug` = (code or None,
-    affine or None) or None, and `crop` = (origin int32 [B][3], patch dims (D, H, W))."""
-    origin, patch = crop
-    code, affine = aug if aug is not None else (None, None)
-    Ds = x_all.shape[1] if x_all.dim() == 5 else 1
-    Hs, Ws = x_all.shape[-3], x_all.shape[-2]
-    patch = tuple(int(v) for v in patch)
-    if patch != tuple(e.sdims(1)):
-        raise ValueError("crop patch %r: the executor's input is %r" % (patch, tuple(e.sdims(1))))
-    if (origin.dtype != torch.int32 or tuple(origin.shape) != (e.B, 3) or origin.device != x_all.device
-            or not origin.is_contiguous()):
-        raise ValueError("crop origins: a contiguous int32 [%d][3] tensor on %s" % (e.B, x_all.device))
-    if code is not None and (code.dtype != torch.int32 or code.numel() != e.B or code.device != x_all.device
-                             or not code.is_contiguous()):
-        raise ValueError("augmentation codes: a contiguous int32 [%d] tensor on %s" % (e.B, x_all.device))
-    if affine is not None and (affine.dtype != torch.float32 or tuple(affine.shape) != (e.B, cin, 2)
-                               or affine.device != x_all.device or not affine.is_contiguous()):
-        raise ValueError("augmentation affine: a contiguous float32 [%d][%d][2] tensor on %s"
-                         % (e.B, cin, x_all.device))
-    ptrs = [_ptr(x_all), _ptr(y_all), _ptr(idx), _ptr(origin), _ptr(code) if code is not None else 0,
-            _ptr(affine) if affine is not None else 0, _ptr(e.bufs["x"]), _ptr(e.target)]
-    return ptrs, [e.B, Ds, Hs, Ws, patch[0], patch[1], patch[2], cin, cpad, K]
-
-
-def has_mat(aug) -> bool:
-    """Whether the augmentation parameters `aug` end in warp matrices: (code, affine, mat)."""
-    return aug is not None and len(aug) > 2 and aug[2] is not None
-
-
-def gather_warp_args(e, x_all, y_all, idx, aug, crop, cin: int, cpad: int, K: int):
-    """(ptrs, ints) of an executor's gather_batch_warp / f32_gather_batch_warp launch
-    (bindings.cpp) from the resident dataset [N, (Ds,) Hs, Ws, Cin], `aug` = (code or None,
-    affine or None, mat int32 [B][4]) and `crop` = (origin int32 [B][3], patch dims (D, H, W)) or
-    None: the patch is then the executor's input at origin 0, which the stored sample must hold."""
-    code, affine, mat = aug
-    Ds = x_all.shape[1] if x_all.dim() == 5 else 1
-    Hs, Ws = x_all.shape[-3], x_all.shape[-2]
-    origin, patch = crop if crop is not None else (None, e.sdims(1))
-    patch = tuple(int(v) for v in patch)
-    if patch != tuple(e.sdims(1)):
-        raise ValueError("crop patch %r: the executor's input is %r" % (patch, tuple(e.sdims(1))))
-    if any(t > s for t, s in zip(patch, (Ds, Hs, Ws))):
-        raise ValueError("the executor's input %r exceeds the stored sample %r" % (patch, (Ds, Hs, Ws)))
-    if (mat.dtype != torch.int32 or tuple(mat.shape) != (e.B, 4) or mat.device != x_all.device
-            or not mat.is_contiguous()):
-        raise ValueError("warp matrices: a contiguous int32 [%d][4] tensor on %s" % (e.B, x_all.device))
-    if origin is not None and (origin.dtype != torch.int32 or tuple(origin.shape) != (e.B, 3)
-                               or origin.device != x_all.device or not origin.is_contiguous()):
-        raise ValueError("crop origins: a contiguous int32 [%d][3] tensor on %s" % (e.B, x_all.device))
-    if code is not None and (code.dtype != torch.int32 or code.numel() != e.B or code.device != x_all.device
-                             or not code.is_contiguous()):
-        raise ValueError("augmentation codes: a contiguous int32 [%d] tensor on %s" % (e.B, x_all.device))
-    if affine is not None and (affine.dtype != torch.float32 or tuple(affine.shape) != (e.B, cin, 2)
-                               or affine.device != x_all.device or not affine.is_contiguous()):
-        raise ValueError("augmentation affine: a contiguous float32 [%d][%d][2] tensor on %s"
-                         % (e.B, cin, x_all.device))
-    ptrs = [_ptr(x_all), _ptr(y_all), _ptr(idx), _ptr(origin) if origin is not None else 0,
-            _ptr(code) if code is not None else 0, _ptr(mat), _ptr(affine) if affine is not None else 0,
-            _ptr(e.bufs["x"]), _ptr(e.target)]
-    return ptrs, [e.B, Ds, Hs, Ws, patch[0], patch[1], patch[2], cin, cpad, K]
-
-
-def plan_case_stats(e, kind: str) -> None:
-    """Buffers and the validation plan of an executor's `case_stats` (kernels/seg_stats.h).
-
-    The op is not part of `plan` / `eval_plan`: `stats_plan` holds it alone (threshold 0.5)
-    so the static plan validation covers its layout and extents on a dry-run executor;
-    `run_case_stats` issues it as an immediate op with the caller's threshold."""
-    K = getattr(e, "K", 1)
-    S = e.npix(1) // e.B
-    e.case_stats_buf = e.case_stats_partial = e.stats_plan = None
-    try:
-        chunks = e.C.seg_stats_chunks(e.B, S, K)
-    except ValueError as err:               # (e.g. 2^24 voxels per sample: fp32 counts not exact)
-        e._case_stats_err = str(err)
-        return
-    e._case_stats_err = None
-    e.case_stats_buf = torch.zeros(e.B, K, 6, dtype=torch.float32, device=e.device)
-    e.case_stats_partial = torch.zeros(max(1, e.B * chunks * 6 * K), dtype=torch.float32, device=e.device)
-    e._case_stats_args = ([_ptr(e.prob), _ptr(e.target), _ptr(e.case_stats_buf), _ptr(e.case_stats_partial)],
-                          [e.B, S, K])
-    e.stats_plan = RecordingPlan(e.C.Plan(getattr(e, "dt_id", 0)))
-    e.stats_plan.add_generic(kind, e._case_stats_args[0], e._case_stats_args[1], [0.5], "case_stats")
-
-
-def run_case_stats(e, kind: str, threshold: float, stream, post: bool = False) -> torch.Tensor:
-    if e._case_stats_err is not None:
-        raise ValueError(e._case_stats_err)
-    if e._dry:
-        raise RuntimeError("executor built with dry_run=True: case_stats is validated, not launched")
-    ptrs, ints = _post_args(e, e._case_stats_args) if post else e._case_stats_args
-    e.C.generic(kind, ptrs, ints, [float(threshold)], native.stream_handle(stream), getattr(e, "dt_id", 0))
-    return e.case_stats_buf
-
-
-# cap of an executor's surf_dist scratch: the field is 8 bytes per (voxel, class) of a sample
-# group, 384 MiB for K = 3 at b1024 128x128.  256 MiB keeps the 3D b8 128^3 K = 1 batch
-# (128 MiB) and the 2D b1024 K = 1 batch (128 MiB) in one group and splits only the
-# multi-class b1024 batches, into 2 groups of 512 samples that still fill the GPU.
-SURF_SCRATCH_CAP = 256 << 20
-
-
-def surf_dist_group(N: int, sample_bytes: int, scratch_bytes: int) -> int:
-    """Samples per surf_dist launch when the scratch holds `scratch_bytes` and one sample
-    needs `sample_bytes`: the fewest groups that fit, of equal size but for the last."""
-    fit = min(N, scratch_bytes // sample_bytes)
-    if fit < 1:
-        raise ValueError("surf_dist: the scratch (%d bytes) does not hold one sample (%d bytes)"
-                         % (scratch_bytes, sample_bytes))
-    groups = -(-N // fit)
-    return -(-N // groups)
-
-
-def launch_surf_dist(C, kind: str, ptrs, ints, threshold: float, scratch_bytes: int, target_bytes: int,
-                     stream=0, dt_id: int = 0) -> int:
-    """Issue `surf_dist` / `f32_surf_dist` (bindings.cpp) over N samples as immediate ops on
-    groups of consecutive samples that fit the scratch.  ptrs = [prob, target, surf, scratch],
-    ints = [N, D, H, W, K]; `target_bytes`: the target's element size.  prob, target and surf
-    are sample-major, so a group is a pointer offset.  Returns the number of launches."""
-    N, D, H, W, K = ints
-    S = D * H * W
-    g = surf_dist_group(N, C.surf_dist_scratch(1, D, H, W, K), scratch_bytes)
-    prob, tgt, surf, scratch = ptrs
-    n0 = launches = 0
-    while n0 < N:
-        n = min(g, N - n0)
-        C.generic(kind, [prob + n0 * S * K * 4, tgt + n0 * S * K * target_bytes, surf + n0 * K * 16, scratch],
-                  [n, D, H, W, K], [float(threshold)], stream, dt_id)
-        n0 += n
-        launches += 1
-    return launches
-
-
-def plan_case_surface(e, kind: str) -> None:
-    """Buffers and the validation plan of an executor's `case_surface` (kernels/surf_dist.h):
-    the int32 [B][K][4] output and the field scratch, min(one batch, SURF_SCRATCH_CAP).
-
-    Like `case_stats` the op is in neither `plan` nor `eval_plan`: `surface_plan` holds the
-    op of the first sample group alone (threshold 0.5) for the static plan validation."""
-    K = getattr(e, "K", 1)
-    d, h, w = e.sdims(1)
-    e.surface_plan = e.case_surface_buf = e.case_surface_scratch = None
-    try:
-        need = e.C.surf_dist_scratch(e.B, d, h, w, K)
-        group = surf_dist_group(e.B, need // e.B, min(need, SURF_SCRATCH_CAP))
-    except ValueError as err:
-        e._case_surface_err = str(err)
-        return
-    e._case_surface_err = None
-    e._case_surface_group = group
-    e.case_surface_buf = torch.zeros(e.B, K, 4, dtype=torch.int32, device=e.device)
-    e.case_surface_scratch = torch.empty(need // e.B * group // 4, dtype=torch.int32, device=e.device)
-    e._case_surface_args = ([_ptr(e.prob), _ptr(e.target), _ptr(e.case_surface_buf), _ptr(e.case_surface_scratch)],
-                            [e.B, d, h, w, K])
-    e.surface_plan = RecordingPlan(e.C.Plan(getattr(e, "dt_id", 0)))
-    e.surface_plan.add_generic(kind, e._case_surface_args[0], [group, d, h, w, K], [0.5], "case_surface")
-
-
-def run_case_surface(e, kind: str, threshold: float, stream, post: bool = False) -> torch.Tensor:
-    if e._dry:
-        raise RuntimeError("executor built with dry_run=True: case_surface is validated, not launched")
-    if e.surface_plan is None and getattr(e, "_case_surface_err", None) is None:
-        plan_case_surface(e, kind)
-    if e._case_surface_err is not None:
-        raise ValueError(e._case_surface_err)
-    ptrs, ints = _post_args(e, e._case_surface_args) if post else e._case_surface_args
-    launch_surf_dist(e.C, kind, ptrs, ints, threshold, e.case_surface_scratch.numel() * 4,
-                     e.target.element_size(), native.stream_handle(stream), getattr(e, "dt_id", 0))
-    return e.case_surface_buf
-
-
-def plan_tta(e, finish_kind: str) -> None:
-    """Buffers and the validation plan of an executor's `evaluate_tta` (kernels/tta.h): the
-    accumulator, the size of `prob`, and the finish's block partials.  Like `case_stats` the
-    ops are in neither `plan` nor `eval_plan`: `tta_plan` holds one tta_acc that writes, one
-    that adds and the finish (M = 4) for the static plan validation; the [M][B] code rows of
-    a code set are made on its first use."""
-    K = getattr(e, "K", 1)
-    d, h, w = e.sdims(1)
-    total = e.prob.numel()
-    e.tta_acc_buf = torch.empty_like(e.prob)
-    e.tta_partial = torch.zeros(e.C.tta_finish_blocks(total) * 4, dtype=torch.float32, device=e.device)
-    e._tta_rows = {}
-    e._tta_finish_kind = finish_kind
-    e._tta_acc_args = ([_ptr(e.prob), _ptr(e.tta_acc_buf)], [e.B, d, h, w, K])
-    e._tta_finish_args = ([_ptr(e.prob), _ptr(e.tta_acc_buf), _ptr(e.target), _ptr(e.tta_partial), _ptr(e.sums)],
-                          [total])
-    e.tta_plan = RecordingPlan(e.C.Plan(getattr(e, "dt_id", 0)))
-    ptrs, ints = e._tta_acc_args
-    # (code 1 = FW: the strip path; code 5 = T | FW: the tile path)
-    e.tta_plan.add_generic("tta_acc", ptrs, ints + [1, 0], [], "tta_acc:write")
-    e.tta_plan.add_generic("tta_acc", ptrs, ints + [5, 1], [], "tta_acc:add")
-    e.tta_plan.add_generic(finish_kind, e._tta_finish_args[0], e._tta_finish_args[1], [0.25], "tta_finish")
-
-
-def run_evaluate_tta(e, x: torch.Tensor, y: torch.Tensor, codes, stream=None) -> None:
-    """Test-time augmentation of one batch x [B, (D,) H, W, Cin], y [B, (D,) H, W, K] over the
-    transform codes `codes` (data/augment.py tta_codes: a power of two of them, the identity
-    last).  Per non-identity code: the augmenting gather loads the transformed batch, the
-    evaluation plan runs, tta_acc brings `prob` back by the inverse code into the accumulator
-    (the first writes it, the others add).  The identity pass goes through the same gather,
-    then tta_finish forms the mean in place.  Afterwards `prob` holds the mean, `target` the
-    stored target and `sums` the sums of the mean (BCE from the probabilities), so
-    `case_stats`, `case_surface` and `probs()` work unchanged."""
-    from ..data.augment import inverse_code
-    if e._dry:
-        raise RuntimeError("executor built with dry_run=True: evaluate_tta is validated, not launched")
-    codes = tuple(int(c) for c in codes)
-    M = len(codes)
-    if M < 2 or M & (M - 1) or codes[-1] != 0 or 0 in codes[:-1] or len(set(codes)) != M:
-        raise ValueError("evaluate_tta: a power of two >= 2 of distinct codes with the identity last, got %r"
-                         % (codes,))
-    if x.shape[0] != e.B:
-        raise ValueError("evaluate_tta takes the executor's batch of %d samples, got %d" % (e.B, x.shape[0]))
-    if getattr(e, "tta_plan", None) is None:
-        plan_tta(e, "f32_tta_finish" if e.dtype == "fp32" else "tta_finish")
-    # (inputs that are not fp32 / contiguous / on the device are converted first)
-    x = x.to(e.device, torch.float32).contiguous()
-    y = y.to(e.device, torch.float32).contiguous()
-    rows = e._tta_rows.get(codes)
-    if rows is None:
-        rows = e._tta_rows[codes] = torch.tensor(codes, dtype=torch.int32).view(M, 1).repeat(1, e.B).to(e.device)
-    if getattr(e, "_iota", None) is None:
-        e._iota = torch.arange(e.B, device=e.device, dtype=torch.int64)
-    s, dt = native.stream_handle(stream), getattr(e, "dt_id", 0)
-    ptrs, ints = e._tta_acc_args
-    for i, c in enumerate(codes):
-        e.load_indexed(x, y, e._iota, stream, aug=(rows[i], None))
-        e.evaluate_batch(stream)
-        if c:
-            e.C.generic("tta_acc", ptrs, ints + [inverse_code(c), 1 if i else 0], [], s, dt)
-    e.C.generic(e._tta_finish_kind, e._tta_finish_args[0], e._tta_finish_args[1], [1.0 / M], s, dt)
-
-
-def plan_sliding(e) -> None:
-    """Buffers and the validation plan of an executor's `predict_sliding` (kernels/sliding.h,
-    `ops.sliding` is the definition): the fp32 staging batch `sw_x` of B tiles of the model's
-    size that `sw_extract` fills and the plain load consumes, the zero target that rides
-    along, and the device weight maps `sw_w` [constant, gaussian].  Like `case_stats` the ops
-    are in neither `plan` nor `eval_plan`: `sw_plan` holds the ops of a probe geometry -- one
-    image a quarter tile wider than the tile at overlap 0.5, two tiles with the second clamped
-    -- for the static plan validation; the accumulator and summed weights of a real call
-    are made per geometry by `run_predict_sliding`."""
-    from ..ops import sliding
-    K, cin = getattr(e, "K", 1), e.spec.in_channels
-    T = e.sdims(1)
-    sp = T if e.dims == 3 else T[1:]
-    e.sw_x = torch.zeros((e.B,) + sp + (cin,), dtype=torch.float32, device=e.device)
-    e.sw_y = torch.zeros((e.B,) + sp + (K,), dtype=torch.float32, device=e.device)
-    e.sw_w = torch.stack([sliding.weight_map(T, b) for b in sliding.BLENDS]).to(e.device)
-    e._sw_run = None
-    dims = (T[0], T[1], T[2] + max(1, T[2] // 4))
-    stride = sliding.strides(T, 0.5)
-    e.sw_src = torch.zeros((1,) + dims + (cin,), dtype=torch.float32, device=e.device)
-    e.sw_acc = torch.zeros((1,) + dims + (K,), dtype=torch.float32, device=e.device)
-    e.sw_wsum = sliding.weight_sum(dims, T, stride, "gaussian").to(e.device)
-    e.sw_plan = RecordingPlan(e.C.Plan(getattr(e, "dt_id", 0)))
-    total = sliding.tiles_per_image(dims, T, stride)
-    for t0 in range(0, total, e.B):
-        tail = list(T) + list(stride) + [e.B, t0, min(e.B, total - t0)]
-        e.sw_plan.add_generic("sw_extract", [_ptr(e.sw_src), _ptr(e.sw_x)], [1] + list(dims) + [cin] + tail, [],
-                              "sw_extract:%d" % t0)
-        e.sw_plan.add_generic("sw_blend", [_ptr(e.prob), _ptr(e.sw_w[1]), _ptr(e.sw_acc)],
-                              [1] + list(dims) + [K] + tail, [], "sw_blend:%d" % t0)
-    e.sw_plan.add_generic("sw_finish", [_ptr(e.sw_acc), _ptr(e.sw_wsum)], [1] + list(dims) + [K], [], "sw_finish")
-
-
-def run_predict_sliding(e, x_dev: torch.Tensor, overlap: float = 0.5, blend: str = "gaussian", tta_codes=(),
-                        stream=None) -> torch.Tensor:
-    """Sliding-window probabilities of the images x_dev [N, (D,) H, W, Cin] of any spatial size
-    (`ops.sliding`): zero the accumulator; per batch of B tiles `sw_extract` fills the staging
-    batch, the evaluation forward runs on it (the plain load and plan, or `evaluate_tta` over
-    `tta_codes`) and `sw_blend` adds the weighted probabilities; `sw_finish` divides by the
-    summed weights.  Everything is issued in order on one stream, so every pixel's sum runs
-    in ascending tile order, as the oracle's.  Returns fp32 [N, (D,) H, W, K] on the device:
-    the executor's buffer, overwritten by the next call of the same geometry."""
-    from ..ops import sliding
-    if e._dry:
-        raise RuntimeError("executor built with dry_run=True: predict_sliding is validated, not launched")
-    sliding.check_blend(blend)
-    T = e.sdims(1)
-    stride = sliding.strides(T, overlap)
-    K, cin = getattr(e, "K", 1), e.spec.in_channels
-    if x_dev.dim() != e.dims + 2 or x_dev.shape[-1] != cin or x_dev.shape[0] < 1:
-        raise ValueError("predict_sliding: images [n, %sH, W, %d], got shape %r"
-                         % ("D, " if e.dims == 3 else "", cin, tuple(x_dev.shape)))
-    if getattr(e, "sw_plan", None) is None:
-        plan_sliding(e)
-    x = x_dev.to(e.device, torch.float32).contiguous()
-    N = x.shape[0]
-    dims = tuple(x.shape[1:4]) if e.dims == 3 else (1,) + tuple(x.shape[1:3])
-    key = (N, dims, stride, blend)
-    run = e._sw_run
-    if run is None or run["key"] != key:
-        e._sw_run = None                      # (the previous geometry's buffers go first)
-        run = e._sw_run = dict(key=key, acc=torch.empty((N,) + dims + (K,), dtype=torch.float32, device=e.device),
-                               wsum=sliding.weight_sum(dims, T, stride, blend).to(e.device))
-    acc, w = run["acc"], e.sw_w[sliding.BLENDS.index(blend)]
-    total = N * sliding.tiles_per_image(dims, T, stride)
-    s, dt = native.stream_handle(stream), getattr(e, "dt_id", 0)
-    with torch.cuda.stream(stream) if stream is not None else _nullctx():
-        acc.zero_()
-    head = [N] + list(dims)
-    for t0 in range(0, total, e.B):
-        tail = list(T) + list(stride) + [e.B, t0, min(e.B, total - t0)]
-        e.C.generic("sw_extract", [_ptr(x), _ptr(e.sw_x)], head + [cin] + tail, [], s, dt)
-        if tta_codes:
-            e.evaluate_tta(e.sw_x, e.sw_y, tta_codes, stream)
-        else:
-            e.load_batch(e.sw_x, e.sw_y, stream)
-            e.evaluate_batch(stream)
-        e.C.generic("sw_blend", [_ptr(e.prob), _ptr(w), _ptr(acc)], head + [K] + tail, [], s, dt)
-    e.C.generic("sw_finish", [_ptr(acc), _ptr(run["wsum"])], head + [K], [], s, dt)
-    return acc if e.dims == 3 else acc.view((N,) + dims[1:] + (K,))
-
-
-def sliding_stats(e, prob: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, stream=None) -> torch.Tensor:
-    """[N][K][6] = {I, St, Sp, TP, FP, FN} per (image, class) of full-size probabilities
-    prob [N, (D,) H, W, K] (`run_predict_sliding`'s result) against the fp32 target y of the
-    same shape: the `f32_seg_stats` op at the images' own size (fp32), or `case_stats_torch` on
-    the device (float64) where the op refuses the shape (S % 8, S >= 2^24, N S K >= 2^31)."""
-    from ..ops import seg_metrics
-    prob, y = prob.contiguous(), y.to(prob.device, torch.float32).contiguous()
-    N, K = prob.shape[0], prob.shape[-1]
-    S = prob[0].numel() // K
-    try:
-        chunks = e.C.seg_stats_chunks(N, S, K)
-    except ValueError:
-        return seg_metrics.case_stats_torch(prob, y, threshold)
-    out = torch.zeros(N, K, 6, dtype=torch.float32, device=prob.device)
-    part = torch.zeros(max(1, N * chunks * 6 * K), dtype=torch.float32, device=prob.device)
-    e.C.generic("f32_seg_stats", [_ptr(prob), _ptr(y), _ptr(out), _ptr(part)], [N, S, K], [float(threshold)],
-                native.stream_handle(stream), 0)
-    return out
-
-
-def sliding_surface(e, prob: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, stream=None) -> torch.Tensor:
-    """int32 [N][K][4] = {mp, mt, q_lo, q_hi} per (image, class) of full-size probabilities
-    against the fp32 target y: `f32_surf_dist` at the images' own size in groups that fit
-    SURF_SCRATCH_CAP, or `case_surface_torch` on the device where the op refuses the shape."""
-    from ..ops import seg_metrics
-    prob, y = prob.contiguous(), y.to(prob.device, torch.float32).contiguous()
-    N, K = prob.shape[0], prob.shape[-1]
-    d, h, w = tuple(prob.shape[1:4]) if prob.dim() == 5 else (1,) + tuple(prob.shape[1:3])
-    try:
-        one = e.C.surf_dist_scratch(1, d, h, w, K)
-        e.C.surf_dist_scratch(N, d, h, w, K)
-        group = surf_dist_group(N, one, max(one, min(one * N, SURF_SCRATCH_CAP)))
-    except ValueError:
-        return seg_metrics.case_surface_torch(prob, y, threshold).to(torch.int32)
-    out = torch.zeros(N, K, 4, dtype=torch.int32, device=prob.device)
-    scratch = torch.empty(one * group // 4, dtype=torch.int32, device=prob.device)
-    launch_surf_dist(e.C, "f32_surf_dist", [_ptr(prob), _ptr(y), _ptr(out), _ptr(scratch)], [N, d, h, w, K],
-                     threshold, scratch.numel() * 4, 4, native.stream_handle(stream), 0)
-    return out
-
-
-# cap of an executor's components scratch: 8 bytes per (voxel, class) of a sample group (the
-# int32 label and size planes), as surf_dist's fields: the same 256 MiB, the same groups
-COMP_SCRATCH_CAP = SURF_SCRATCH_CAP
-
-
-def components_group(C, N: int, D: int, H: int, W: int, K: int, cap: int = COMP_SCRATCH_CAP) -> int:
-    """Samples per `components` launch under the byte cap `cap` (at least one sample): the
-    fewest groups that fit, of equal size but for the last.  ValueError with the op's reason
-    where it refuses the shape."""
-    C.components_scratch(1, D, H, W, K)                   # (the op's refusal of the shape, if any)
-    lo, hi = 1, N                                         # the most samples whose scratch fits the cap
-    while lo < hi:
-        mid = (lo + hi + 1) // 2
-        if C.components_scratch(mid, D, H, W, K) <= cap:
-            lo = mid
-        else:
-            hi = mid - 1
-    groups = -(-N // lo)
-    return -(-N // groups)
-
-
-def launch_components(C, ptrs, ints, threshold: float, keep_largest: bool, min_size: int, group: int,
-                      stream=0) -> int:
-    """Issue `components` (bindings.cpp) over N samples as immediate ops on groups of `group`
-    consecutive samples.  ptrs = [prob, out, info, scratch], ints = [N, D, H, W, K]; prob, out
-    and info are sample-major, so a group is a pointer offset; the scratch holds
-    components_scratch(group, ...) bytes.  Returns the number of launches (6 kernels each)."""
-    N, D, H, W, K = ints
-    S = D * H * W
-    prob, out, info, scratch = ptrs
-    n0 = launches = 0
-    while n0 < N:
-        n = min(group, N - n0)
-        C.generic("components", [prob + n0 * S * K * 4, out + n0 * S * K * 4, info + n0 * K * 16, scratch],
-                  [n, D, H, W, K, int(bool(keep_largest)), int(min_size)], [float(threshold)], stream, 0)
-        n0 += n
-        launches += 1
-    return launches
-
-
-def plan_components(e) -> None:
-    """Buffers and the validation plan of an executor's `components` (kernels/components.h):
-    `prob_pp` (the size of `prob`), the int32 [B][K][4] `components_info` and the scratch of
-    one sample group under COMP_SCRATCH_CAP.  Also the second argument sets of `case_stats`
-    / `case_surface`, which score `prob_pp` in place of `prob`.
-
-    Like `case_stats` the op is in neither `plan` nor `eval_plan`: `components_plan` holds the
-    op of the first sample group alone (threshold 0.5, keep the largest) for the static plan
-    validation."""
-    K = getattr(e, "K", 1)
-    d, h, w = e.sdims(1)
-    e.components_plan = e.prob_pp = e.components_info = e.components_scratch = None
-    try:
-        group = components_group(e.C, e.B, d, h, w, K)
-        need = e.C.components_scratch(group, d, h, w, K)
-    except ValueError as err:
-        e._components_err = str(err)
-        return
-    e._components_err = None
-    e._components_group = group
-    e.prob_pp = torch.zeros_like(e.prob)
-    e.components_info = torch.zeros(e.B, K, 4, dtype=torch.int32, device=e.device)
-    e.components_scratch = torch.empty(need // 4, dtype=torch.int32, device=e.device)
-    e._components_args = ([_ptr(e.prob), _ptr(e.prob_pp), _ptr(e.components_info), _ptr(e.components_scratch)],
-                          [e.B, d, h, w, K])
-    e.components_plan = RecordingPlan(e.C.Plan(getattr(e, "dt_id", 0)))
-    e.components_plan.add_generic("components", e._components_args[0], [group, d, h, w, K, 1, 0], [0.5],
-                                  "components")
-
-
-def _post_args(e, args):
-    """The argument set (ptrs, ints) of `case_stats` / `case_surface` with `prob_pp` for `prob`."""
-    if getattr(e, "prob_pp", None) is None:
-        raise RuntimeError("no filtered probabilities: call components() before scoring prob_pp")
-    ptrs, ints = args
-    return [_ptr(e.prob_pp)] + list(ptrs[1:]), ints
-
-
-def run_components(e, threshold: float, keep_largest: bool, min_size: int, stream) -> torch.Tensor:
-    if e._dry:
-        raise RuntimeError("executor built with dry_run=True: components is validated, not launched")
-    if not 0.0 < float(threshold) < 1.0:
-        raise ValueError("components: threshold strictly inside (0, 1)")
-    if int(min_size) < 0:
-        raise ValueError("components: min_size >= 0")
-    if e.components_plan is None and getattr(e, "_components_err", None) is None:
-        plan_components(e)
-    if e._components_err is not None:
-        raise ValueError(e._components_err)
-    ptrs, ints = e._components_args
-    launch_components(e.C, ptrs, ints, threshold, keep_largest, min_size, e._components_group,
-                      native.stream_handle(stream))
-    return e.components_info
-
-
-def sliding_components(e, prob: torch.Tensor, threshold: float = 0.5, keep_largest: bool = True, min_size: int = 0,
-                       stream=None, cap: int = COMP_SCRATCH_CAP):
-    """(out fp32 like prob, info int32 [N][K][4]) of full-size probabilities prob [N, (D,) H, W, K]
-    (`run_predict_sliding`'s result): the `components` op at the images' own size in groups
-    that fit `cap`, or `components_torch` on the device where the op refuses the shape."""
-    from ..ops import components as cc
-    prob = prob.contiguous()
-    N, K = prob.shape[0], prob.shape[-1]
-    d, h, w = tuple(prob.shape[1:4]) if prob.dim() == 5 else (1,) + tuple(prob.shape[1:3])
-    try:
-        if e.C.components_check(N, d, h, w, K, int(min_size)) is not None:
-            raise ValueError
-        group = components_group(e.C, N, d, h, w, K, cap)
-    except ValueError:
-        out, info = cc.components_torch(prob, threshold, keep_largest, min_size)
-        return out, info
-    out = torch.empty_like(prob)
-    info = torch.zeros(N, K, 4, dtype=torch.int32, device=prob.device)
-    scratch = torch.empty(e.C.components_scratch(group, d, h, w, K) // 4, dtype=torch.int32, device=prob.device)
-    launch_components(e.C, [_ptr(prob), _ptr(out), _ptr(info), _ptr(scratch)], [N, d, h, w, K], threshold,
-                      keep_largest, min_size, group, native.stream_handle(stream))
-    return out, info

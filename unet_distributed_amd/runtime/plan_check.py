@@ -452,8 +452,8 @@ def check_tta_plan(e) -> List[str]:
     finish.  They read the probabilities the evaluation plan left behind and the loaded
     target; the accumulator must be the size of `prob` and the partial buffer hold one row
     per block of the finish."""
-    if getattr(e, "tta_plan", None) is None:
-        return ["evaluate_tta is not planned (plan_tta)"]
+    if e.tta_plan is None:
+        return ["evaluate_tta is not planned (ExecutorBase.plan_tta)"]
     errs = check_plan(e, e.tta_plan, False, extra_inputs=("prob",))
     if e.tta_acc_buf.numel() != e.prob.numel() or e.tta_acc_buf.dtype != torch.float32:
         errs.append("evaluate_tta: tta_acc_buf holds %d floats, prob %d" % (e.tta_acc_buf.numel(), e.prob.numel()))
@@ -464,14 +464,14 @@ def check_tta_plan(e) -> List[str]:
 
 
 def check_sliding_plan(e) -> List[str]:
-    """Errors of executor `e`'s sliding-window ops (`sw_plan`, built by `plan_sliding` on first
+    """Errors of executor `e`'s sliding-window ops (`sw_plan`, built by `e.plan_sliding()` on first
     use): per batch of its probe geometry an sw_extract into the staging batch and an sw_blend
     of the probabilities the evaluation plan leaves behind, then the sw_finish.  The probe
     images, the weight maps and the summed weights are inputs; the accumulator is zeroed
     before the first batch.  The staging batch must hold one batch of fp32 tiles and the
     accumulator every image of the probe."""
-    if getattr(e, "sw_plan", None) is None:
-        return ["predict_sliding is not planned (plan_sliding)"]
+    if e.sw_plan is None:
+        return ["predict_sliding is not planned (ExecutorBase.plan_sliding)"]
     errs = check_plan(e, e.sw_plan, False, extra_inputs=("prob", "sw_src", "sw_w", "sw_wsum", "sw_acc"))
     d, h, w = e.sdims(1)
     need = e.B * d * h * w * e.spec.in_channels
@@ -485,10 +485,10 @@ def check_surface_plan(e) -> List[str]:
     with --eval_hd95): like `case_stats` it reads the probabilities the forward /
     evaluation plan left behind and the loaded target.  The plan holds the op of the first
     group of samples; the output must hold every group's rows and the scratch one group."""
-    if getattr(e, "surface_plan", None) is None:
-        return [getattr(e, "_case_surface_err", None) or "case_surface is not planned (plan_case_surface)"]
+    if e.surface_plan is None:
+        return [e._case_surface_err or "case_surface is not planned (ExecutorBase.plan_case_surface)"]
     errs = check_plan(e, e.surface_plan, False, extra_inputs=("prob",))
-    K, (d, h, w) = getattr(e, "K", 1), e.sdims(1)
+    K, (d, h, w) = e.K, e.sdims(1)
     if e.case_surface_buf.numel() < e.B * K * 4:
         errs.append("case_surface: case_surface_buf holds %d ints, B K 4 = %d needed"
                     % (e.case_surface_buf.numel(), e.B * K * 4))
@@ -506,10 +506,10 @@ def check_components_plan(e) -> List[str]:
     and writes `prob_pp`, `components_info` and the scratch.  The plan holds the op of the
     first group of samples; `prob_pp` must be the size of `prob`, the info hold every group's
     rows and the scratch one group."""
-    if getattr(e, "components_plan", None) is None:
-        return [getattr(e, "_components_err", None) or "components is not planned (plan_components)"]
+    if e.components_plan is None:
+        return [e._components_err or "components is not planned (ExecutorBase.plan_components)"]
     errs = check_plan(e, e.components_plan, False, extra_inputs=("prob",))
-    K, (d, h, w) = getattr(e, "K", 1), e.sdims(1)
+    K, (d, h, w) = e.K, e.sdims(1)
     if e.prob_pp.numel() != e.prob.numel() or e.prob_pp.dtype != torch.float32:
         errs.append("components: prob_pp holds %d floats, prob %d" % (e.prob_pp.numel(), e.prob.numel()))
     if e.components_info.numel() < e.B * K * 4:
