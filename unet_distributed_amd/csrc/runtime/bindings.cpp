@@ -832,6 +832,27 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
       return unet::components_launch(prob, n, d, h, w, K, thr, largest, min_size, scratch, out, info, s);
     };
   }
+  if (kind == "labelmap") {
+    // ptrs: prob (fp32 [N][D][H][W][K]), out (uint8 [N][Do][Ho][Wo]), counts (int32 [N][5], zeroed by the op)
+    // ints: N, D, H, W, K, Do, Ho, Wo, od, oh, ow, rule (0 nested, 1 argmax), values (values[m] in byte m - 1)
+    // floats: threshold
+    need(3, 13, 1);
+    check_msg(unet::labelmap_check(I[0], I[1], I[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9], I[10], I[11], I[12],
+                                   F[0]));
+    const float* prob = (const float*)vp(0);
+    uint8_t* out = (uint8_t*)vp(1);
+    int* counts = (int*)vp(2);
+    if (!prob || !out || !counts) throw std::invalid_argument("labelmap: prob / out / counts required");
+    if ((P[0] | P[2]) & 3) throw std::invalid_argument("labelmap: prob and counts must be aligned to 4 bytes");
+    const int n = (int)I[0], d = (int)I[1], h = (int)I[2], w = (int)I[3], K = (int)I[4];
+    const int dd = (int)I[5], hd = (int)I[6], wd = (int)I[7], od = (int)I[8], oh = (int)I[9], ow = (int)I[10];
+    const int rule = (int)I[11];
+    const unsigned values = (unsigned)I[12];
+    const float thr = (float)F[0];
+    return [=](hipStream_t s) {
+      return unet::labelmap_launch(prob, n, d, h, w, K, dd, hd, wd, od, oh, ow, rule, values, thr, out, counts, s);
+    };
+  }
   if (kind == "norm_moments") {
     // ptrs: A, B, partial, S  ints: N, P, C    (S[n][2][C] = per-sample sums of A and A*B)
     need(4, 3, 0);
@@ -1219,6 +1240,15 @@ PYBIND11_MODULE(_C, m) {
     const char* msg = unet::components_check(N, D, H, W, K, min_size);
     return msg ? py::object(py::str(msg)) : py::object(py::none());
   }, py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("K"), py::arg("min_size") = 0);
+  // labelmap_check: the reason a labelmap launch is refused, or None (values: values[m] in byte m - 1)
+  m.def("labelmap_check", [](long long N, long long D, long long H, long long W, long long K, long long Do,
+                             long long Ho, long long Wo, long long od, long long oh, long long ow, long long rule,
+                             long long values, double threshold) {
+    const char* msg = unet::labelmap_check(N, D, H, W, K, Do, Ho, Wo, od, oh, ow, rule, values, threshold);
+    return msg ? py::object(py::str(msg)) : py::object(py::none());
+  }, py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("K"), py::arg("Do"), py::arg("Ho"),
+        py::arg("Wo"), py::arg("od"), py::arg("oh"), py::arg("ow"), py::arg("rule"), py::arg("values"),
+        py::arg("threshold") = 0.5);
   m.def("norm_blocks_per_sample", &norm_blocks_per_sample);
   m.def("sample_slices", &sample_slices);
   m.def("row_slices", &row_slices);

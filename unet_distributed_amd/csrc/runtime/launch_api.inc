@@ -254,4 +254,12 @@ const char* components_check(long long N, long long D, long long H, long long W,
 long long components_scratch(long long N, long long D, long long H, long long W, long long K);
 hipError_t components_launch(const float* prob, int N, int D, int H, int W, int K, float thr, int keep_largest,
                              int min_size, int* scratch, float* out, int* info, hipStream_t s);
+// label maps from probabilities (labelmap.h, f32_labelmap.hip): prob fp32 [N][D][H][W][K] -> out uint8
+// [N][Do][Ho][Wo], the source pasted at (od, oh, ow) and 0 elsewhere; counts int32 [N][5]: source
+// voxels per slot (zeroed by the launch).  rule 0 nested, 1 argmax; values: values[m] in byte m - 1
+const char* labelmap_check(long long N, long long D, long long H, long long W, long long K, long long Do, long long Ho,
+                           long long Wo, long long od, long long oh, long long ow, long long rule, long long values,
+                           double thr);
+hipError_t labelmap_launch(const float* prob, int N, int D, int H, int W, int K, int Do, int Ho, int Wo, int od, int oh,
+                           int ow, int rule, unsigned values, float thr, uint8_t* out, int* counts, hipStream_t s);
 hipError_t f32_transpose_launch(const float* src, int T, int A, int B, int flip, float* dst, hipStream_t s);

@@ -27,39 +27,49 @@ def load_data(data_path: str, prefix: str = "_train"):
     return imgs, msks
 
 
-def update_channels(imgs, msks, input_no=1, output_no=1, mode=1):
-    """Channel-last selection (`preprocess.py:287-350`), returns float32 arrays."""
-    shp = imgs.shape
-    new_imgs = np.zeros((shp[0], shp[1], shp[2], input_no), dtype=np.float32)
-    new_msks = np.zeros((shp[0], shp[1], shp[2], output_no), dtype=np.float32)
+def select_images(imgs, input_no=1, mode=1):
+    """The image half of `update_channels`: float32 [..., input_no] of [..., 4] modalities."""
+    new_imgs = np.zeros(tuple(imgs.shape[:-1]) + (input_no,), dtype=np.float32)
     if mode == 1:
         new_imgs[..., 0] = imgs[..., 2]                                     # FLAIR
-        new_msks[..., 0] = msks[..., 0] + msks[..., 1] + msks[..., 2] + msks[..., 3]
     elif mode == 2:
         new_imgs[..., 0] = imgs[..., 0]                                     # T1 post
-        new_msks[..., 0] = msks[..., 3]
     elif mode == 3:
         new_imgs[..., 0] = imgs[..., 1]                                     # T2
-        new_msks[..., 0] = msks[..., 0] + msks[..., 2] + msks[..., 3]
-    elif mode == 4:                                                          # [EXT] all modalities
-        k = min(input_no, shp[3])
+    elif mode in (4, 5):                                                     # [EXT] all modalities
+        k = min(input_no, imgs.shape[-1])
         new_imgs[..., :k] = imgs[..., :k]
-        new_msks[..., 0] = msks[..., 0] + msks[..., 1] + msks[..., 2] + msks[..., 3]
+    return new_imgs
+
+
+def select_masks(msks, output_no=1, mode=1, shape=None):
+    """The mask half of `update_channels`: float32 [..., output_no] of the one-hot labels
+    [..., 4] (`shape`: the leading shape, the masks' own by default)."""
+    new_msks = np.zeros(tuple(msks.shape[:-1] if shape is None else shape) + (output_no,), dtype=np.float32)
+    if mode == 2:
+        new_msks[..., 0] = msks[..., 3]
+    elif mode == 3:
+        new_msks[..., 0] = msks[..., 0] + msks[..., 2] + msks[..., 3]
     elif mode == 5:                                                          # [EXT] nested regions out
-        # all modalities in (as mode 4); channel k of the mask is the region of mode 1 / 3 / 2:
-        # whole tumour, core, enhancing (output_no 1..3) -- one model with three sigmoid outputs
+        # channel k of the mask is the region of mode 1 / 3 / 2: whole tumour, core, enhancing
+        # (output_no 1..3) -- one model with three sigmoid outputs
         if not 1 <= output_no <= 3:
             raise ValueError("mode 5 has three nested regions: output_no must be 1..3")
-        k = min(input_no, shp[3])
-        new_imgs[..., :k] = imgs[..., :k]
         regions = (msks[..., 0] + msks[..., 1] + msks[..., 2] + msks[..., 3],
                    msks[..., 0] + msks[..., 2] + msks[..., 3],
                    msks[..., 3])
         for c in range(output_no):
             new_msks[..., c] = regions[c]
-    else:
+    else:                                                                    # modes 1, 4 and any other
         new_msks[..., 0] = msks[..., 0] + msks[..., 1] + msks[..., 2] + msks[..., 3]
-    return new_imgs, new_msks
+    return new_msks
+
+
+def update_channels(imgs, msks, input_no=1, output_no=1, mode=1):
+    """Channel-last selection (`preprocess.py:287-350`), returns float32 arrays: mode 1 FLAIR ->
+    whole tumour, 2 T1c -> enhancing, 3 T2 -> core, 4 [EXT] all modalities -> whole tumour,
+    5 [EXT] all modalities -> the nested regions."""
+    return select_images(imgs, input_no, mode), select_masks(msks, output_no, mode, shape=imgs.shape[:-1])
 
 
 # radius scale of mask channel k of the synthetic lesions (nested regions, like BraTS's

@@ -188,6 +188,61 @@ class Predictor:
         return self._sliding(x, overlap, blend, max_bytes, lambda p, s, t: self.backend.sliding_components(
             p, threshold).long())
 
+    @torch.no_grad()
+    def segment(self, x, threshold: float = 0.5, labels: str = "", overlap: float = 0.5, blend: str = "gaussian",
+                volume: bool = False, out_shape=None, offset=None, max_bytes: int = 1 << 30, mode=None,
+                visit=None):
+        """(labels uint8 ndarray, counts int64 ndarray) of images x [n, (D,) H, W, Cin] of any
+        spatial size: `predict_sliding`'s blended probabilities, the `components=` filter if the
+        Predictor has one, then the label map of `ops.labelmap` under the rule and values of
+        `labels` (the --labels spelling; `mode` picks its defaults) -- all on the device (native:
+        the `labelmap` kernel), so only the uint8 labels are copied to the host.
+
+        volume=False: the images are independent; labels [n, (Do,) Ho, Wo], counts [n][K + 1].
+        volume=True (2D models): the n slices are one case, filtered 6-connected as the volume
+        [1, n, H, W, K]; labels [n, Ho, Wo], counts [1][K + 1].  `out_shape` / `offset`: the label
+        map is pasted at `offset` into a zero destination of `out_shape` ((H, W) pairs, or
+        (D, H, W) triples); None is the source's own shape.  `visit(p, info, s, t)`, if given, is
+        called with the filtered probabilities of the images [s, t) on the device ([1, n, H, W, K]
+        of the whole case with volume=True) and the filter's info (None with the filter off)."""
+        from .ops import labelmap, sliding
+        sliding.check_overlap(overlap)
+        sliding.check_blend(blend)
+        K = self.spec.n_cl_out
+        rule, values = labelmap.parse_labels(labels, K, mode)
+        if volume and self.spec.dims != 2:
+            raise ValueError("segment: volume=True joins the slices of a 2D model; a 3D model's image is a volume")
+        x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32))
+        be = self.backend
+        off = (0, 0, 0) if offset is None else tuple(offset)
+        chunks = self.sliding_chunks(tuple(x.shape), max_bytes)
+        if volume:
+            n = x.shape[0]
+            joined = None
+            for s, t in chunks:
+                p = be.predict_sliding(x[s:t].to(self.device), overlap, blend, post=False)
+                if joined is None:
+                    joined = torch.empty((n,) + tuple(p.shape[1:]), dtype=torch.float32, device=p.device)
+                joined[s:t].copy_(p)          # (the backend's buffer is overwritten by the next chunk)
+            case, info = be.filter_once(joined.unsqueeze(0), threshold)
+            if visit is not None:
+                visit(case, info, 0, n)
+            if out_shape is not None and len(out_shape) == 2:
+                out_shape = (n,) + tuple(out_shape)
+            off = (0,) + off if len(off) == 2 else off
+            lab, counts = be.sliding_labels(case, threshold, rule, values, out_shape, off)
+            return lab[0].cpu().numpy(), counts.long().cpu().numpy()
+        labs, cnts = [], []
+        for s, t in chunks:
+            p = be.predict_sliding(x[s:t].to(self.device), overlap, blend, post=False)
+            p, info = be.filter_once(p, threshold)
+            if visit is not None:
+                visit(p, info, s, t)
+            lab, counts = be.sliding_labels(p, threshold, rule, values, out_shape, off)
+            labs.append(lab.cpu())
+            cnts.append(counts.long().cpu())
+        return torch.cat(labs).numpy(), torch.cat(cnts).numpy()
+
 
 SIGNATURE ="intel_unet_brats_model"
 

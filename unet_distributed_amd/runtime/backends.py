@@ -218,9 +218,27 @@ class TorchBackend:
                                             threshold)
 
     @torch.no_grad()
-    def sliding_surface(self, p, y, threshold: float = 0.5) -> torch.Tensor:
-        """[n][K][4] of full-size probabilities p (`predict_sliding`) against the target y."""
-        return seg_metrics.case_surface_torch(self._filter(p, threshold)[0], y.to(p.device).float(), threshold)
+    def sliding_surface(self, p, y, threshold: float = 0.5, post: bool = True) -> torch.Tensor:
+        """[n][K][4] of full-size probabilities p (`predict_sliding`) against the target y.
+        post=False: of p itself, the --eval_components filter not applied."""
+        return seg_metrics.case_surface_torch(self._filter(p, threshold)[0] if post else p, y.to(p.device).float(),
+                                              threshold)
+
+    @torch.no_grad()
+    def filter_once(self, p, threshold: float = 0.5):
+        """(filtered p, info or None) of the --eval_components filter, the kept last result neither
+        used nor replaced (`Predictor.segment`: a case's map is filtered under another shape)."""
+        if self.components is None:
+            return p, None
+        return cc.components_torch(p, threshold, *self.components)
+
+    @torch.no_grad()
+    def sliding_labels(self, p, threshold: float = 0.5, rule: str = "nested", values=(1,), out_shape=None,
+                       offset=(0, 0, 0)):
+        """(labels uint8, counts int32 [n][K + 1]) of full-size probabilities p (`ops.labelmap`)."""
+        from ..ops import labelmap
+        out, counts = labelmap.labelmap_torch(p, threshold, rule, values, out_shape, offset)
+        return out, counts.to(torch.int32)
 
     def after_optimizer(self):
         pass
@@ -434,10 +452,28 @@ class NativeBackend:
         return sliding_stats(self.engine.C, self._sw_filter(p, threshold)[0] if post else p, y, threshold)
 
     @torch.no_grad()
-    def sliding_surface(self, p, y, threshold: float = 0.5) -> torch.Tensor:
-        """int32 [n][K][4] of full-size probabilities p (`predict_sliding`) against the target y."""
+    def sliding_surface(self, p, y, threshold: float = 0.5, post: bool = True) -> torch.Tensor:
+        """int32 [n][K][4] of full-size probabilities p (`predict_sliding`) against the target y.
+        post=False: of p itself, the --eval_components filter not applied."""
         from .executor_base import sliding_surface
-        return sliding_surface(self.engine.C, self._sw_filter(p, threshold)[0], y, threshold)
+        return sliding_surface(self.engine.C, self._sw_filter(p, threshold)[0] if post else p, y, threshold)
+
+    @torch.no_grad()
+    def filter_once(self, p, threshold: float = 0.5):
+        """(filtered p, info or None) of the --eval_components filter, the kept last result neither
+        used nor replaced (`Predictor.segment`: a case's map is filtered under another shape)."""
+        if self.components is None:
+            return p, None
+        from .executor_base import sliding_components
+        return sliding_components(self.engine.C, p, threshold, *self.components)
+
+    @torch.no_grad()
+    def sliding_labels(self, p, threshold: float = 0.5, rule: str = "nested", values=(1,), out_shape=None,
+                       offset=(0, 0, 0)):
+        """(labels uint8, counts int32 [n][K + 1]) on the device of full-size probabilities p: the
+        `labelmap` op (`executor_base.sliding_labels`)."""
+        from .executor_base import sliding_labels
+        return sliding_labels(self.engine.C, p, threshold, rule, values, out_shape, offset)
 
     def adam_step(self, lr, b1p, b2p, grad_scale=1.0):
         self.engine.adam_step(lr, b1p, b2p, grad_scale)

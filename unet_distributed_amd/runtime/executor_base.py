@@ -25,7 +25,7 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 # ops with one build for both executors (fp32 operands whatever the storage type): issued by
 # their bare name; every other op of this module has an "f32_" twin for the fp32 executor
-UNPREFIXED_OPS = frozenset(("tta_acc", "sw_extract", "sw_blend", "sw_finish", "components"))
+UNPREFIXED_OPS = frozenset(("tta_acc", "sw_extract", "sw_blend", "sw_finish", "components", "labelmap"))
 
 
 def op_kind(name: str, prefix: str) -> str:
@@ -178,6 +178,28 @@ def sliding_components(C, prob: torch.Tensor, threshold: float = 0.5, keep_large
     launch_components(C, [_ptr(prob), _ptr(out), _ptr(info), _ptr(scratch)], [N, d, h, w, K], threshold,
                       keep_largest, min_size, group, native.stream_handle(stream))
     return out, info
+
+
+def sliding_labels(C, prob: torch.Tensor, threshold: float = 0.5, rule: str = "nested", values=(1,),
+                   out_shape=None, offset=(0, 0, 0), stream=None):
+    """(labels uint8 [N, (Do,) Ho, Wo], counts int32 [N][K + 1]) on the device of full-size
+    probabilities prob [N, (D,) H, W, K] (`predict_sliding`'s result, filtered or not), pasted at
+    `offset` into `out_shape` (`ops.labelmap`): the `labelmap` op, or `labelmap_torch` on the
+    device where the op refuses the launch."""
+    from ..ops import labelmap as lm
+    prob = prob.contiguous()
+    N, (d, h, w), K, dst, off = lm.geometry(prob, out_shape, offset)
+    values = lm.check_values(values, K)
+    rule_id = lm.RULES.index(rule) if rule in lm.RULES else -1
+    ints = [N, d, h, w, K] + list(dst) + list(off) + [rule_id, lm.pack_values(values)]
+    if prob.dtype != torch.float32 or C.labelmap_check(*ints, float(threshold)) is not None:
+        out, counts = lm.labelmap_torch(prob, threshold, rule, values, dst, off)
+        return out, counts.to(torch.int32)
+    out = torch.empty((N,) + dst, dtype=torch.uint8, device=prob.device)
+    counts5 = torch.empty(N, 5, dtype=torch.int32, device=prob.device)
+    C.generic("labelmap", [_ptr(prob), _ptr(out), _ptr(counts5)], ints, [float(threshold)],
+              native.stream_handle(stream), 0)
+    return (out if prob.dim() == 5 else out[:, 0]), counts5[:, :K + 1]
 
 
 class ExecutorBase:

@@ -112,6 +112,9 @@ def _generic_write_spans(kind: str, p: List[int], ints: List[int]) -> List[Tuple
     if kind == "components" and len(p) > 3 and len(ints) >= 5:
         N, D, H, W, K = ints[:5]
         return [(p[1], N * D * H * W * K * 4), (p[2], N * K * 4 * 4), (p[3], components_scratch(N, D, H, W, K))]
+    # label map (N, D, H, W, K, Do, Ho, Wo in ints): the whole uint8 destination and N 5 ints of counts
+    if kind == "labelmap" and len(p) > 2 and len(ints) >= 8:
+        return [(p[1], ints[0] * ints[5] * ints[6] * ints[7]), (p[2], ints[0] * 5 * 4)]
     # augmenting batch gather (B, D, H, W, Cin, Cpad, K in ints): the padded input and the target,
     # 16-bit (gather_batch_aug) or fp32 (f32_gather_batch_aug)
     if kind in ("gather_batch_aug", "f32_gather_batch_aug") and len(p) > 6 and len(ints) >= 7:
@@ -234,6 +237,8 @@ def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], Li
         return _sel(p, [0, 1]), _sel(p, [2, 3])
     if kind == "components":
         return _sel(p, [0]), _sel(p, [1, 2, 3])
+    if kind == "labelmap":
+        return _sel(p, [0]), _sel(p, [1, 2])
     if kind in ("gather_batch_aug", "f32_gather_batch_aug"):
         return [q for q in _sel(p, [0, 1, 2, 3, 4]) if q], _sel(p, [5, 6])
     if kind in ("gather_batch_crop", "f32_gather_batch_crop"):
