@@ -1194,7 +1194,8 @@ int conv_fwd_pick(const ConvFwdParams& p) {
   if (p.tile && p.tile != 8) return p.tile;
   // row-window 512x32 wins at every level it applies to (16..128 wide), measured
   // 1.1-2.1x over the implicit-GEMM tiles (profiles/r1_conv_tiles.md); the 512x64
-  // variant needs 287 registers (1 wave/SIMD) and never wins
+  // variant took 287 registers unbounded (1 wave/SIMD) and never won -- bounded to 256 it
+  // runs two workgroups per CU on 32 / 64-wide rows (conv_win.h win_b512_eligible)
   if (p.tile != 8 && win_eligible(p)) return 6;
   if (p.tile != 8 && win_first_eligible(p)) return 9;
   if (p.tile != 8 && img8_eligible(p)) return 13;

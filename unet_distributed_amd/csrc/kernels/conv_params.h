@@ -176,7 +176,9 @@ struct ConvFwdParams {
                               // chunks load the next chunk under the current one's MFMAs
                               // (conv_win_cp_kernel); >= 2: also 128-wide rows, 3D or two or more
                               // chunks (conv_win_cp128_kernel)
-  HeadGrad hg;                // 2D row-window data gradient of the head input: src1 (dY) formed
+  int win_bm2;                // 64-channel row windows of 512 pixels instead of 256 (conv_win.h
+                              // win_b512_eligible): bit 0 on 32-wide rows, bit 1 on 64-wide rows
+  HeadGrad hg;               // 2D row-window data gradient of the head input: src1 (dY) formed
                               // on load (one 32-channel chunk), see HeadGrad
   // Space-to-depth source (2D row-window, composite transposed-conv data gradient):
   // s2d = C > 0 -> src1 is a FINE [N][2H][2W][C] tensor read as the coarse H x W image

@@ -1,6 +1,7 @@
 // Row-window 3x3 conv kernels (fine UNet levels), shared by the instantiation units
-// conv_win_b32.hip (32-channel tiles) and conv_win_b64.hip (64-channel tiles): each
-// builds one launch_win<BN, BM> so the ~150 kernel variants compile in parallel.
+// conv_win_b32.hip (32-channel tiles), conv_win_b64.hip (64-channel tiles) and
+// conv_win_b64_512.hip (64-channel tiles, 512-pixel windows): each builds its
+// launch_win<BN, BM> so the ~160 kernel variants compile in parallel.
 // conv_fwd.hip picks the tile (win_bn / win_bm) and dispatches.
 #pragma once
 #include "common.h"
@@ -27,8 +28,27 @@ inline int win_bn(const ConvFwdParams& p) {
   const int W = p.OW > 128 ? 128 : p.OW;
   return (p.Cout % 64 == 0 && W <= 64 && !p.head_w) ? 64 : 32;
 }
-// Window pixels: 256 for 16-wide rows and for the 64-channel tile (its accumulators,
-// 4 x 4 fragments per wave, and LDS then still fit two workgroups per CU), else 512.
+// 512-pixel window of the 64-channel tile (conv_win_kernel<W, 64, 512>, conv_win_b64_512.hip):
+// p.win_bm2 bit 0 / 1 on 32 / 64-wide 2D whole rows, plain / concat / space-to-depth source,
+// forward (pool epilogue too), data-gradient (masks, pool route) or generic epilogue.  The
+// statistics and dgrad-norm epilogues (one statistics row per 256-pixel window), the
+// operand transforms 1 / 2 / 3 / 5, the fused weight gradient and 3D keep 256 pixels.
+inline bool win_b512_eligible(const ConvFwdParams& p) {
+  const int bit = p.OW == 32 ? 1 : (p.OW == 64 ? 2 : 0);
+  const int ep = conv_epi_mode(p);
+  return (p.win_bm2 & bit) && win_bn(p) == 64 && p.KD == 1 && p.OD == 1 && p.OH % (512 / p.OW) == 0 &&
+         (ep == EPI_FWD || ep == EPI_DGRAD || ep == EPI_GENERIC) && !p.xform && !p.hg.prob && !p.ut.x &&
+         !p.fw.x && !p.head_w;
+}
+// Window pixels: 256 for 16-wide rows (one whole image: a window never spans two) and for
+// the 64-channel tile (4 x 4 accumulator fragments per wave), else 512.  The 64-channel
+// tile at 512 pixels (win_b512_eligible: 8 x 4 accumulators = 128 registers + 48 of weight
+// fragments under a 256-register bound, 77 / 79 KB LDS at W = 32 / 64 -- still two
+// workgroups per CU) halves the workgroups: on the headline step the summed 32-wide launches
+// fell 10.3 % and the 64-wide ones 8.8 % (there against the chunk-pipelined 256-pixel
+// window), -0.6 ms per step (profiles/r18_win512.md).  Of a workgroup's ~13 us outside its
+// chunks only ~12 % amortises (the rest is per-pixel staging and stores); the other part
+// of the gain is the 36 KB weight image staged per chunk half as often per pixel.
 // (A 256-pixel 32-channel window on 32..128-wide rows -- three workgroups per CU --
 // measured -0.4 % at W = 64 and -1 % at 128 and was dropped; a pipelined 8-wave window
 // with double-buffered chunks, one workgroup per CU, measured -2..-21 % per launch at
@@ -36,6 +56,7 @@ inline int win_bn(const ConvFwdParams& p) {
 // wait with the other's MFMAs, AND its prologue / epilogue, which one workgroup cannot.)
 inline int win_bm(const ConvFwdParams& p) {
   const int W = p.OW > 128 ? 128 : p.OW;
+  if (win_b512_eligible(p)) return 512;
   return (W == 16 || win_bn(p) == 64) ? 256 : 512;
 }
 inline int win_rows(const ConvFwdParams& p) {
@@ -58,9 +79,11 @@ constexpr int CP_DZ_MAXC = 128;      // conv_win_cp_kernel DZ: input channels in
 // Chunk-pipelined window (conv_win_cp_kernel): 2D 64-wide full rows, the 64-channel tile,
 // plain or concat source, no operand transform, two or more 32-channel input chunks (level 2
 // of the 128^2 UNet).  (At levels 3-4 -- 32 / 16-wide rows, 4..16 chunks -- the per-launch
-// times rose 0.016-0.034 ms against the DMA chunk loop, run V: not used there.)
+// times rose 0.016-0.034 ms against the DMA chunk loop, run V: not used there.)  It is a
+// 256-pixel window: the register prefetch of a 512-pixel halo does not fit beside 128
+// accumulators, so a 512-pixel window (win_b512_eligible) runs the DMA chunk loop.
 inline bool win_cp_eligible(const ConvFwdParams& p) {
-  return p.win_cp > 0 && p.OW == 64 && p.KD == 1 && p.OD == 1 &&
+  return p.win_cp > 0 && p.OW == 64 && p.KD == 1 && p.OD == 1 && !win_b512_eligible(p) &&
          p.C1 + p.C2 >= 64 && p.Cout % 64 == 0 && !p.head_w && p.tile != 6 &&
          (!p.xform || (p.xform == 2 && !p.C2 && p.C1 <= CP_DZ_MAXC)) && !p.hg.prob &&
          !p.s2d && !p.ut.x && !p.fw.x;
@@ -93,14 +116,18 @@ inline int win_grid(const ConvFwdParams& p) {
   return ((rows + R - 1) / R) * (p.OW / W) * (p.Cout / win_bn(p));
 }
 // (BN, BM, row width) combinations win_bn / win_bm can select (the 64-channel tile also
-// on 128-wide rows: tile 12 forces it there for tests)
+// on 128-wide rows: tile 12 forces it there for tests; its 512-pixel window on 32 / 64-wide
+// rows only -- 16-wide rows would span two images, 128-wide ones need 90 KB of LDS)
 template <int BN, int BM>
 constexpr bool win_tile_built(int W) {
-  return BN == 64 ? BM == 256 : (BM == 256 ? W == 16 : W != 16);
+  return BN == 64 ? (BM == 256 || (BM == 512 && (W == 32 || W == 64))) : (BM == 256 ? W == 16 : W != 16);
 }
 
 template <int BN, int BM>
 hipError_t launch_win(const ConvFwdParams& p, hipStream_t s);
+// launch_win<64, 256> hands win_b512_eligible convs to the 512-pixel unit (conv_fwd.hip
+// dispatches on the channel tile alone)
+extern template hipError_t launch_win<64, 512>(const ConvFwdParams& p, hipStream_t s);
 
 // fused data + weight gradient window (conv_dw.hip, tile 14; conv_params.h FusedWgrad)
 const char* conv_dw_check(const ConvFwdParams& p);
@@ -144,8 +171,10 @@ constexpr int NTHR = 256;
 // DMA gathers the fine pixels of each coarse slot, structurally zero taps skipped); 5
 // (2D concat): the src1 chunks are the transposed conv u = tconv2x2s2(p.ut.x) + b formed
 // in LDS (conv_params.h TconvSrc), the src2 (skip) chunks are DMA'd as usual.
+// The 512 x 64 tile is bounded to 256 registers (two waves per SIMD, the occupancy its LDS
+// allows): unbounded it took 268-287 and ran one workgroup per CU.
 template <int W, int BN, int BM, bool CONCAT, int EPI, int GEO, int XF = 0>
-__global__ void __launch_bounds__(NTHR) conv_win_kernel(const ConvFwdParams p) {
+__global__ void __launch_bounds__(NTHR, (BN == 64 && BM == 512) ? 2 : 1) conv_win_kernel(const ConvFwdParams p) {
   static_assert(BN == 32 || BN == 64, "row-window tile is 32 or 64 output channels wide");
   static_assert(XF == 0 || ((XF == 1 || XF == 2 || XF == 3 || XF == 4) && GEO == GEO_2D && !CONCAT) ||
                     (XF == 5 && GEO == GEO_2D && CONCAT) || (XF == 3 && GEO == GEO_3D && !CONCAT),
@@ -1696,10 +1725,53 @@ hipError_t launch_win_pf(const ConvFwdParams& p, hipStream_t s) {
   return launch_status();
 }
 
+// 512-pixel window of the 64-channel tile (win_b512_eligible): the LDS-DMA chunk loop of
+// conv_win_kernel on W-wide 2D whole rows
+template <int W>
+hipError_t launch_win_b512(const ConvFwdParams& p, hipStream_t s) {
+  if (!win_b512_eligible(p) || p.OW != W) return hipErrorInvalidValue;
+  const int grid = win_grid(p);
+  const int epi = conv_epi_mode(p);
+  if (p.s2d) {                          // space-to-depth dgrad source (conv_fwd_prepare checks the shape)
+    if (epi != EPI_DGRAD || p.C2) return hipErrorInvalidValue;
+    UNET_LAUNCH((conv_win_kernel<W, 64, 512, false, EPI_DGRAD, GEO_2D, 4>), dim3(grid), dim3(NTHR), 0, s, p);
+    return launch_status();
+  }
+#define B512_EPI(CC)                                                                                      \
+  if (epi == EPI_FWD)                                                                                     \
+    UNET_LAUNCH((conv_win_kernel<W, 64, 512, CC, EPI_FWD, GEO_2D>), dim3(grid), dim3(NTHR), 0, s, p);     \
+  else if (epi == EPI_DGRAD)                                                                              \
+    UNET_LAUNCH((conv_win_kernel<W, 64, 512, CC, EPI_DGRAD, GEO_2D>), dim3(grid), dim3(NTHR), 0, s, p);   \
+  else                                                                                                    \
+    UNET_LAUNCH((conv_win_kernel<W, 64, 512, CC, EPI_GENERIC, GEO_2D>), dim3(grid), dim3(NTHR), 0, s, p);
+  if (p.C2 > 0) {
+    B512_EPI(true)
+  } else {
+    B512_EPI(false)
+  }
+#undef B512_EPI
+  return launch_status();
+}
+
 }  // namespace
 
 template <int BN, int BM>
+static hipError_t launch_win_tile(const ConvFwdParams& p, hipStream_t s);
+
+template <int BN, int BM>
 hipError_t launch_win(const ConvFwdParams& p, hipStream_t s) {
+  if constexpr (BN == 64 && BM == 512) {
+    return p.OW == 32 ? launch_win_b512<32>(p, s) : (p.OW == 64 ? launch_win_b512<64>(p, s) : hipErrorInvalidValue);
+  } else {
+    if constexpr (BN == 64 && BM == 256) {
+      if (win_b512_eligible(p)) return launch_win<64, 512>(p, s);
+    }
+    return launch_win_tile<BN, BM>(p, s);
+  }
+}
+
+template <int BN, int BM>
+static hipError_t launch_win_tile(const ConvFwdParams& p, hipStream_t s) {
   if constexpr (BN == 32 && BM == 512) {
     if (win_pf_eligible(p)) return launch_win_pf(p, s);
     if (win_pfu_eligible(p)) return launch_win_pfu(p, s);

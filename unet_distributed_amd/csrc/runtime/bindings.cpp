@@ -106,7 +106,8 @@ ConvFwdParams conv_params(const py::dict& d) {
   p.rev = get<int>(d, "rev", 0);
   p.win_pf = get<int>(d, "win_pf", 0);
   p.win_cp = get<int>(d, "win_cp", 0);
-  p.dst1 = const_cast<void*>(getp(d, "dst1"));
+  p.win_bm2 = get<int>(d, "win_bm2", 0);
+  p.dst1= const_cast<void*>(getp(d, "dst1"));
   p.dst2 = const_cast<void*>(getp(d, "dst2"));
   p.D1 = get<int>(d, "D1", p.Cout);
   p.mask1 = getp(d, "mask1");
