@@ -104,10 +104,12 @@ class Config:
     loss_scale: float = 0.0          # fp16 static loss scale (0 = dynamic)
     eval_threshold: float = 0.5      # probability threshold of the per-case (hard) evaluation metrics
     eval_hd95: bool = False          # evaluation also reports the per-case 95th-percentile Hausdorff distance
-    augment: str = ""                # training batches only: comma-separated subset of flip, rot90, intensity, rotate, scale
+    augment: str = ""                # training batches only: comma-separated subset of flip, rot90, intensity, rotate, scale, elastic
     augment_intensity: float = 0.1   # intensity: scale in [1-a, 1+a], shift in [-a, a] per (sample, channel)
     augment_rotate: float = 30.0     # rotate: angle uniform in [-r, r] degrees per sample, r in (0, 180]
     augment_scale: float = 0.25      # scale: zoom log-uniform in [1/(1+a), 1+a] per sample, a in (0, 1]
+    augment_elastic: float = 4.0     # elastic: standard deviation of a control node's displacement, stored-image pixels
+    augment_elastic_cell: int = 32   # elastic: side of a control-lattice cell in patch pixels, 8, 16, 32 or 64
     eval_tta: str = ""               # evaluation only: mean prediction over flip and / or rot90 (comma-separated)
     eval_components: str = ""        # evaluation only: connected-component filter, comma list of largest, min:V
     crop: str = ""                   # training patches of img_size from larger stored images: random | foreground[:P]
@@ -138,8 +140,9 @@ _CHOICES = {
 }
 
 
-AUGMENT_NAMES = ("flip", "rot90", "intensity", "rotate", "scale")
+AUGMENT_NAMES = ("flip", "rot90", "intensity", "rotate", "scale", "elastic")
 SPATIAL_NAMES = ("rotate", "scale")  # the transforms that resample the image (data/augment.py draw_spatial)
+ELASTIC_CELLS = (8, 16, 32, 64)      # --augment_elastic_cell (data/augment.py draw_elastic)
 
 
 def parse_augment(s: str) -> tuple:
@@ -290,5 +293,16 @@ def validate(cfg: Config) -> None:
     if not 0.0 < cfg.augment_scale <= 1.0:
         raise SystemExit("--augment_scale must be in (0, 1]: the zoom is drawn from [1/(1+a), 1+a], got %r"
                          % (cfg.augment_scale,))
+    if "elastic" in parse_augment(cfg.augment):
+        # node values are truncated at +-2a, so neighbouring nodes differ by at most 4a and the
+        # quadratic B-spline's derivative is at most 4a / S: a <= S / 8 keeps it within 1/2
+        S, a = cfg.augment_elastic_cell, cfg.augment_elastic
+        if S not in ELASTIC_CELLS:
+            raise SystemExit("--augment_elastic_cell must be one of %s, got %r" % (", ".join(map(str, ELASTIC_CELLS)), S))
+        if not a > 0.0:
+            raise SystemExit("--augment_elastic must be positive: the nodes' standard deviation in pixels, got %r" % (a,))
+        if not a <= S / 8.0:
+            raise SystemExit("--augment_elastic must be at most --augment_elastic_cell / 8 = %g (the displacement's "
+                             "gradient stays within 1/2), got %r" % (S / 8.0, a))
     if cfg.mode == 5 and cfg.out_channels > 3:
         raise SystemExit("--mode 5 has three nested regions: --out_channels must be 1..3")

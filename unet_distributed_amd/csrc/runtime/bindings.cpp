@@ -286,6 +286,7 @@ F32Wgrad f32_wgrad_params(const py::dict& d) {
   X(gather_batch_aug_launch) \
   X(gather_batch_crop_launch) \
   X(gather_batch_warp_launch) \
+  X(gather_batch_elastic_launch) \
   X(maxpool2_fwd_launch) \
   X(norm_pool_launch) \
   X(maxpool2_bwd_launch) \
@@ -440,6 +441,34 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
     return [=](hipStream_t s) {
       return A->gather_batch_warp_launch(xa, ya, ix, org, code, mat, aff, B, Ds, Hs, Ws, D, H, W, cin, cpad, K, xb, tb,
                                          s);
+    };
+  }
+  if (kind == "gather_batch_elastic" || kind == "f32_gather_batch_elastic") {
+    // ptrs: x_all, y_all, idx (int64), origin (int32 [B][3] or 0), code (int32 [B] or 0), mat (int32
+    //       [B][4], Q16, or 0 = the identity), affine (fp32 [B][Cin][2] or 0), field (int32
+    //       [B][N][N][2], N = ((H - 1) >> s) + 3), xb, tb (gather_batch_elastic: the 16-bit type,
+    //       f32_gather_batch_elastic: fp32)
+    // ints: B, Ds, Hs, Ws, D, H, W, Cin, Cpad, K, s (log2 of the cell side)
+    need(10, 11, 0);
+    check_msg(gather_elastic_check(I[0], I[1], I[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9], I[10]));
+    const float *xa = (const float*)vp(0), *ya = (const float*)vp(1);
+    const long long* ix = (const long long*)vp(2);
+    const int *org = (const int*)vp(3), *code = (const int*)vp(4), *mat = (const int*)vp(5);
+    const float* aff = (const float*)vp(6);
+    const int* fld = (const int*)vp(7);
+    void *xb = vp(8), *tb = vp(9);
+    if (!xa || !ya || !ix || !fld || !xb || !tb)
+      throw std::invalid_argument("gather_batch_elastic: x_all / y_all / idx / field / xb / tb required");
+    int B = I[0], Ds = I[1], Hs = I[2], Ws = I[3], D = I[4], H = I[5], W = I[6], cin = I[7], cpad = I[8], K = I[9];
+    int sl = I[10];
+    if (kind == "f32_gather_batch_elastic")
+      return [=](hipStream_t s) {
+        return unet::f32_gather_batch_elastic_launch(xa, ya, ix, org, code, mat, aff, fld, B, Ds, Hs, Ws, D, H, W, cin,
+                                                     cpad, K, sl, (float*)xb, (float*)tb, s);
+      };
+    return [=](hipStream_t s) {
+      return A->gather_batch_elastic_launch(xa, ya, ix, org, code, mat, aff, fld, B, Ds, Hs, Ws, D, H, W, cin, cpad, K,
+                                            sl, xb, tb, s);
     };
   }
   if (kind == "pool_fwd") {

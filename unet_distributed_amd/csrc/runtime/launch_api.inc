@@ -50,6 +50,16 @@ hipError_t gather_batch_warp_launch(const float* x_all, const float* y_all, cons
                                     const int* code, const int* mat, const float* affine, int B, int Ds, int Hs,
                                     int Ws, int D, int H, int W, int Cin, int Cpad, int K, void* xb, void* tb,
                                     hipStream_t s);
+// gather_batch_warp with a per-pixel displacement added to the source coordinates: a quadratic
+// B-spline through field int32 [B][N][N][2] (2^-17 pixel, entries clamped into [-2^22, 2^22] by the
+// kernel), N = ((H - 1) >> s) + 3, cells of 1 << s patch pixels (gather_elastic.h); mat may be null
+// (= the identity), origin and code as in the warp
+const char* gather_elastic_check(long long B, long long Ds, long long Hs, long long Ws, long long D, long long H,
+                                 long long W, long long Cin, long long Cpad, long long K, long long s);
+hipError_t gather_batch_elastic_launch(const float* x_all, const float* y_all, const long long* idx,
+                                       const int* origin, const int* code, const int* mat, const float* affine,
+                                       const int* field, int B, int Ds, int Hs, int Ws, int D, int H, int W, int Cin,
+                                       int Cpad, int K, int s, void* xb, void* tb, hipStream_t st);
 // code: optional uint32 per (pooled pixel, 8 channels) = first-argmax index per channel
 // (2 / 3 bits); the backward reads it instead of x when non-null
 hipError_t maxpool2_fwd_launch(const void* x, int N, int D, int H, int W, int C, int dims3, void* y, void* code,
@@ -240,6 +250,11 @@ hipError_t f32_gather_batch_warp_launch(const float* x_all, const float* y_all, 
                                         const int* origin, const int* code, const int* mat, const float* affine, int B,
                                         int Ds, int Hs, int Ws, int D, int H, int W, int Cin, int Cpad, int K,
                                         float* xb, float* tb, hipStream_t s);
+// gather_batch_elastic with fp32 outputs (f32_gather_elastic.hip)
+hipError_t f32_gather_batch_elastic_launch(const float* x_all, const float* y_all, const long long* idx,
+                                           const int* origin, const int* code, const int* mat, const float* affine,
+                                           const int* field, int B, int Ds, int Hs, int Ws, int D, int H, int W,
+                                           int Cin, int Cpad, int K, int s, float* xb, float* tb, hipStream_t st);
 // surf_dist with an fp32 target (f32_surf_dist.hip)
 hipError_t f32_surf_dist_launch(const float* prob, const float* t, int N, int D, int H, int W, int K, float thr,
                                 int* field, int* surf, hipStream_t s);

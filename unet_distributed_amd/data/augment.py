@@ -28,6 +28,16 @@ isotropic zoom in the (H, W) plane: :func:`draw_spatial` draws it from hash word
 image, nearest target, zero outside the image) in integer coordinates, and the whole transform
 is ``apply_torch(*warp_torch(x, y, origin, patch, mat), code, affine)`` -- the oracle of
 ``csrc/kernels/gather_warp.h``.
+
+``--augment elastic`` adds a smooth random deformation: :func:`draw_elastic` draws a lattice of
+control-node displacements per sample (``--augment_elastic`` pixels of standard deviation, cells
+of ``--augment_elastic_cell`` patch pixels) from hash words of its own, :func:`elastic_disp`
+evaluates the integer quadratic B-spline through them at every patch pixel, and
+:func:`elastic_torch` is warp_torch with that displacement added to its source coordinates (the
+matrix is the identity without rotate / scale).  The whole transform is
+``apply_torch(*elastic_torch(x, y, origin, patch, mat, field, S), code, affine)`` -- the oracle
+of ``csrc/kernels/gather_elastic.h``.  The order stays crop, resample, flip / quarter turns,
+jitter.
 """
 
 from typing import Callable, Optional, Sequence, Tuple
@@ -234,23 +244,31 @@ def warp_torch(x, y, origin, patch, mat):
     ``apply_torch(*warp_torch(x, y, origin, patch, mat), code, affine)`` straight from the stored
     samples -- taps outside the patch rectangle read the stored image -- and the oracle of
     ``csrc/kernels/gather_warp.h``."""
+    return _resample("warp_torch", x, y, origin, patch, mat, None)
+
+
+def _resample(who, x, y, origin, patch, mat, disp):
+    """warp_torch's body; `mat` None is the identity, `disp` = None or a function (n, H, W, device)
+    -> (dh, dw) int64 [n, H, W] added to the source coordinates Qh, Qw (elastic_torch)."""
     import torch
     n = x.shape[0]
     D, H, W = _dims3(patch)
     three_d = x.dim() == 5
     Ds, Hs, Ws = tuple(x.shape[1:4]) if three_d else (1,) + tuple(x.shape[1:3])
     if not three_d and D != 1:
-        raise ValueError("warp_torch: 2D samples take a patch of depth 1")
+        raise ValueError("%s: 2D samples take a patch of depth 1" % who)
     if D > Ds or H > Hs or W > Ws:
-        raise ValueError("warp_torch: patch %r exceeds the stored sample %r" % ((D, H, W), (Ds, Hs, Ws)))
+        raise ValueError("%s: patch %r exceeds the stored sample %r" % (who, (D, H, W), (Ds, Hs, Ws)))
+    if mat is None:
+        mat = np.tile(np.array([MAT_ONE, 0, 0, MAT_ONE], dtype=np.int64), (n, 1))
     m = np.asarray(mat.cpu() if isinstance(mat, torch.Tensor) else mat).reshape(-1, 4).astype(np.int64)
     if origin is None:
         org = np.zeros((n, 3), dtype=np.int64)
     else:
         org = np.asarray(origin.cpu() if isinstance(origin, torch.Tensor) else origin).reshape(-1, 3).astype(np.int64)
     if len(m) != n or len(org) != n or y.shape[0] != n:
-        raise ValueError("warp_torch: %d matrices and %d origins for %d images and %d targets"
-                         % (len(m), len(org), n, y.shape[0]))
+        raise ValueError("%s: %d matrices and %d origins for %d images and %d targets"
+                         % (who, len(m), len(org), n, y.shape[0]))
     dev = x.device
     m = torch.from_numpy(np.clip(m, -MAT_MAX, MAT_MAX)).to(dev)
     org = torch.from_numpy(np.clip(org, 0, np.array([Ds - D, Hs - H, Ws - W], dtype=np.int64)[None, :])).to(dev)
@@ -259,6 +277,9 @@ def warp_torch(x, y, origin, patch, mat):
     a = [m[:, e].view(n, 1, 1) for e in range(4)]
     qh = (org[:, 1].view(n, 1, 1) << 17) + (H - 1) * 65536 + a[0] * u + a[1] * v
     qw = (org[:, 2].view(n, 1, 1) << 17) + (W - 1) * 65536 + a[2] * u + a[3] * v
+    if disp is not None:
+        dh, dw = disp(n, H, W, dev)
+        qh, qw = qh + dh, qw + dw
     # the D slices of every sample, pixels flattened: [n, D, Hs Ws, C]
     dsel = org[:, 0].view(n, 1) + torch.arange(D, dtype=torch.int64, device=dev).view(1, D)
 
@@ -287,6 +308,106 @@ def warp_torch(x, y, origin, patch, mat):
     if not three_d:
         xo, yo = xo.squeeze(1), yo.squeeze(1)
     return xo.contiguous(), yo.contiguous()
+
+
+# first hash lane of draw_elastic's words: past draw's, draw_crop's and draw_spatial's, so codes,
+# affines, origins and matrices are the same with and without elastic
+_ELASTIC_LANE = 1 << 18
+FIELD_MAX = 1 << 22                  # every field entry is clamped into [-FIELD_MAX, FIELD_MAX] (32 pixels) before use
+# standard deviation of the sum of a word's four 16-bit fields: each is uniform on 0..65535
+_ELASTIC_SD = float(np.sqrt(((1 << 32) - 1) / 3.0))
+
+
+def elastic_log2(S) -> int:
+    """s = log2 S of a control-lattice cell side S in {8, 16, 32, 64}; ValueError otherwise."""
+    S = int(S)
+    if S not in (8, 16, 32, 64):
+        raise ValueError("elastic cell side: 8, 16, 32 or 64 patch pixels, got %r" % (S,))
+    return S.bit_length() - 1
+
+
+def elastic_nodes(side: int, S: int) -> int:
+    """Control nodes along a patch axis of `side` pixels: ((side - 1) >> s) + 3."""
+    return ((int(side) - 1) >> elastic_log2(S)) + 3
+
+
+def _hw(patch_hw) -> Tuple[int, int]:
+    if isinstance(patch_hw, (int, np.integer)):
+        return int(patch_hw), int(patch_hw)
+    return tuple(int(v) for v in tuple(patch_hw)[-2:])
+
+
+def draw_elastic(seed: int, step: int, sample_idx, patch_hw, a: float = 4.0, S: int = 32) -> np.ndarray:
+    """field int32 [n][Nh][Nw][2] of the dataset samples `sample_idx` at global step `step`: the
+    displacement of control node (i, j) of the patch's quadratic B-spline lattice along h (entry 0)
+    and w (entry 1), in 2^-17 pixel of the stored image.  `patch_hw` = (H, W) (or one side) of the
+    patch, N = ((side - 1) >> log2 S) + 3 nodes per axis, cells of S patch pixels.  The same
+    counter hash as :func:`draw` with words of its own, one per entry in (i, j, c) order.  A word
+    becomes a near-Gaussian without libm: t = the sum of its four 16-bit fields, g = (t - 131070)
+    / sqrt((2^32 - 1) / 3), entry = clip(rint(131072 a g), -2a 131072, 2a 131072): standard
+    deviation `a` pixels, truncated at two of them."""
+    H, W = _hw(patch_hw)
+    nh, nw = elastic_nodes(H, S), elastic_nodes(W, S)
+    idx = np.asarray(sample_idx, dtype=np.int64).reshape(-1)
+    h = _hash(seed, step, idx, nh * nw * 2, first=_ELASTIC_LANE)
+    m = np.uint64(0xFFFF)
+    t = ((h & m) + ((h >> np.uint64(16)) & m) + ((h >> np.uint64(32)) & m) + (h >> np.uint64(48))).astype(np.int64)
+    g = (t - 131070).astype(np.float64) / _ELASTIC_SD
+    lim = 2.0 * float(a) * 131072.0
+    return np.clip(np.rint(131072.0 * float(a) * g), -lim, lim).astype(np.int32).reshape(len(idx), nh, nw, 2)
+
+
+def elastic_disp(field, patch_hw, S: int, device=None):
+    """(dh, dw) int64 tensors [n, H, W]: the displacement of every patch pixel (h', w') under
+    `field` int [n][Nh][Nw][2] (entries clamped into [-2^22, 2^22]), in 2^-17 pixel.  With
+    ci = h' >> s, t = h' & (S - 1) the integer quadratic B-spline weights are
+    wh = [(S - t)^2, -2 t^2 + 2 S t + S^2, t^2] (sum 2 S^2), ww alike from w', and
+    d_c = (sum_a wh[a] sum_b ww[b] f[ci + a][cj + b][c]) >> (2 + 4 s) -- an arithmetic shift of an
+    int64 sum below 2^48 -- so a constant field displaces by exactly that constant."""
+    import torch
+    s = elastic_log2(S)
+    H, W = _hw(patch_hw)
+    f = torch.as_tensor(np.asarray(field.cpu() if isinstance(field, torch.Tensor) else field).astype(np.int64))
+    if f.dim() != 4 or tuple(f.shape[1:]) != (elastic_nodes(H, S), elastic_nodes(W, S), 2):
+        raise ValueError("elastic field: [n][%d][%d][2] for a %d x %d patch at cell %d, got %r"
+                         % (elastic_nodes(H, S), elastic_nodes(W, S), H, W, S, tuple(f.shape)))
+    f = f.clamp(-FIELD_MAX, FIELD_MAX).to(device if device is not None else "cpu")
+    n, dev = f.shape[0], f.device
+
+    def weights(side):
+        p = torch.arange(side, dtype=torch.int64, device=dev)
+        t = p & (S - 1)
+        return p >> s, torch.stack([(S - t) * (S - t), -2 * t * t + 2 * S * t + S * S, t * t])
+
+    ci, wh = weights(H)
+    cj, ww = weights(W)
+    acc = torch.zeros(n, H, W, 2, dtype=torch.int64, device=dev)
+    for a in range(3):
+        rows = f[:, ci + a]                                       # [n, H, Nw, 2]
+        inner = torch.zeros(n, H, W, 2, dtype=torch.int64, device=dev)
+        for b in range(3):
+            inner = inner + ww[b].view(1, 1, W, 1) * rows[:, :, cj + b]
+        acc = acc + wh[a].view(1, H, 1, 1) * inner
+    d = acc >> (2 + 4 * s)
+    return d[..., 0].contiguous(), d[..., 1].contiguous()
+
+
+def elastic_torch(x, y, origin, patch, mat, field, S: int):
+    """warp_torch with a smooth per-pixel displacement: the patches of batch tensors x [n, (Ds,) Hs,
+    Ws, C] and y (any device) at `origin` (None: 0), read through `mat` int [n][4] (None: the
+    identity) at source coordinates Qh = (warp_torch's Qh) + d_0, Qw = (warp_torch's Qw) + d_1 with
+    (d_0, d_1) = :func:`elastic_disp` of `field` int [n][Nh][Nw][2] (draw_elastic) at the patch
+    pixel.  From Q on everything is warp_torch's: taps, weights, one fp32 rounding per op, nearest
+    target, zero outside the stored image; every depth slice of a sample uses the same field.
+    The whole training transform is ``apply_torch(*elastic_torch(...), code, affine)`` -- the
+    displacement is indexed by the patch pixel before the flip / transpose code -- and the oracle
+    of ``csrc/kernels/gather_elastic.h``."""
+    import torch
+    fl = field.cpu() if isinstance(field, torch.Tensor) else field
+    if len(fl) != x.shape[0]:
+        raise ValueError("elastic_torch: %d fields for %d images" % (len(fl), x.shape[0]))
+    return _resample("elastic_torch", x, y, origin, patch, mat,
+                     lambda n, H, W, dev: tuple(d.view(n, H, W) for d in elastic_disp(fl, (H, W), S, dev)))
 
 
 def inverse_code(code: int) -> int:
@@ -367,14 +488,24 @@ def tta_mean_torch(predict_fn, x, codes):
 def make_aug(cfg, step: int) -> Optional[Callable[[Sequence[int]], Tuple[np.ndarray, Optional[np.ndarray]]]]:
     """The per-step callable a DeviceFeeder takes (dataset sample indices -> parameters),
     or None when --augment is off.  With `rotate` or `scale` named the parameters gain the warp
-    matrices as a last item: (code, affine, mat)."""
+    matrices as a last item: (code, affine, mat).  With `elastic` named they are (code, affine,
+    mat or None, field): the matrices' slot is always there, the field (draw_elastic) comes last."""
     names = parse_augment(cfg.augment)
     if not names:
         return None
-    if not has_spatial(names):
-        return lambda idx: draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity)
-    return lambda idx: draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity) + (
-        draw_spatial(cfg.seed, step, idx, names, cfg.augment_rotate, cfg.augment_scale),)
+    side = (cfg.img_size, cfg.img_size)
+
+    def fn(idx):
+        out = draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity)
+        spatial = has_spatial(names)
+        if spatial:
+            out = out + (draw_spatial(cfg.seed, step, idx, names, cfg.augment_rotate, cfg.augment_scale),)
+        if "elastic" in names:
+            out = out + (() if spatial else (None,)) + (
+                draw_elastic(cfg.seed, step, idx, side, cfg.augment_elastic, cfg.augment_elastic_cell),)
+        return out
+
+    return fn
 
 
 def has_spatial(names) -> bool:
@@ -385,7 +516,8 @@ def has_spatial(names) -> bool:
 def make_crop_aug(cfg, step: int, stored, table=None):
     """make_aug's sibling for --crop: dataset sample indices -> (code, affine, origin).  The
     codes are all zero and the affine None when --augment is off; the origins are draw_crop's.
-    With `rotate` or `scale` named: (code, affine, origin, mat)."""
+    With `rotate` or `scale` named: (code, affine, origin, mat).  With `elastic` named:
+    (code, affine, origin, mat or None, field)."""
     mode, p_fg = parse_crop(cfg.crop)
     names = parse_augment(cfg.augment)
     patch = (cfg.img_size,) * 3 if cfg.dims == 3 else (1, cfg.img_size, cfg.img_size)
@@ -393,9 +525,13 @@ def make_crop_aug(cfg, step: int, stored, table=None):
     def fn(idx):
         code, affine = draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity)
         origin, _ = draw_crop(cfg.seed, step, idx, stored, patch, mode, p_fg, table)
-        if has_spatial(names):
-            return code, affine, origin, draw_spatial(cfg.seed, step, idx, names, cfg.augment_rotate,
-                                                      cfg.augment_scale)
+        mat = draw_spatial(cfg.seed, step, idx, names, cfg.augment_rotate, cfg.augment_scale) \
+            if has_spatial(names) else None
+        if "elastic" in names:
+            return code, affine, origin, mat, draw_elastic(cfg.seed, step, idx, patch[1:], cfg.augment_elastic,
+                                                           cfg.augment_elastic_cell)
+        if mat is not None:
+            return code, affine, origin, mat
         return code, affine, origin
 
     return fn

@@ -11,7 +11,7 @@ for sequential reads.  ``--num_threads`` (README.md:63) sizes the gather pool.
 import numpy as np
 import torch
 
-from .augment import apply_torch, crop_torch, warp_torch
+from .augment import apply_torch, crop_torch, elastic_torch, warp_torch
 
 
 class BatchLoader:
@@ -74,15 +74,21 @@ class ResidentBatch:
     optional (origin int32 [n][3] on the device, patch dims (D, H, W)): the batch is the patch
     of each stored sample at its origin (--crop), cropped before it is augmented.  An `aug` of three
     items ends in the warp matrices (mat int32 [n][4], --augment rotate / scale): the patch, or the
-    whole sample without `crop`, is resampled through them straight from the stored sample."""
+    whole sample without `crop`, is resampled through them straight from the stored sample.  An `aug`
+    of four items (code, affine, mat or None, field int32 [n][N][N][2], --augment elastic) adds the
+    elastic displacement of each sample's field, a lattice of `elastic_cell` patch pixels per cell."""
 
-    def __init__(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, aug=None, crop=None):
+    def __init__(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, aug=None, crop=None,
+                 elastic_cell: int = 32):
         self.x_all, self.y_all, self.idx = x_all, y_all, idx
         self.aug = aug
         self.crop = crop
+        self.elastic_cell = int(elastic_cell)
 
     def tensors(self):
         x, y = self.x_all.index_select(0, self.idx), self.y_all.index_select(0, self.idx)
+        if self.aug is not None and len(self.aug) > 3:
+            return elastic_batch(x, y, self.crop, *self.aug, S=self.elastic_cell)
         if self.aug is not None and len(self.aug) > 2 and self.aug[2] is not None:
             return warp_batch(x, y, self.crop, *self.aug)
         if self.crop is not None:
@@ -108,6 +114,14 @@ def warp_batch(x, y, crop, code, affine, mat):
     return apply_torch(x, y, code if code is not None else np.zeros(x.shape[0], dtype=np.int32), affine)
 
 
+def elastic_batch(x, y, crop, code, affine, mat, field, S: int = 32):
+    """warp_batch with an elastic field (cells of S patch pixels): elastic_torch, whose `mat` may be
+    None (the identity), then apply_torch(code or the identity, affine)."""
+    origin, patch = crop if crop is not None else (None, tuple(x.shape[1:-1]))
+    x, y = elastic_torch(x, y, origin, patch, mat, field, S)
+    return apply_torch(x, y, code if code is not None else np.zeros(x.shape[0], dtype=np.int32), affine)
+
+
 class DeviceFeeder:
     """Per-step batches on the training device.
 
@@ -122,10 +136,12 @@ class DeviceFeeder:
     """
 
     def __init__(self, x: np.ndarray, y: np.ndarray, per_rank: int, device, threads: int = 8,
-                 mode: str = "auto", budget_frac: float = 0.25, patch=None):
+                 mode: str = "auto", budget_frac: float = 0.25, patch=None, elastic_cell: int = 32):
         """`patch`: optional (D, H, W) of the training patches (--crop): every batch is then
-        cut out of the stored samples at the origins its `aug` callable returns."""
+        cut out of the stored samples at the origins its `aug` callable returns.  `elastic_cell`:
+        the cell side of the fields an `aug` callable may return (--augment_elastic_cell)."""
         self.device = torch.device(device)
+        self.elastic_cell = int(elastic_cell)
         self.per_rank = per_rank
         self.patch = None if patch is None else tuple(int(v) for v in patch)
         nbytes = (x.size + y.size) * 4
@@ -146,11 +162,13 @@ class DeviceFeeder:
         self.events = [None] * len(self.loaders)
         self.k = 0
 
-    def _upload(self, sorted_idx: np.ndarray, code: np.ndarray, affine, origin=None, mat=None):
+    def _upload(self, sorted_idx: np.ndarray, code: np.ndarray, affine, origin=None, mat=None, field=None):
         """Index tensor and augmentation parameters in one small non-blocking copy:
-        [idx int64 | affine fp32 | code int32 | origin int32 | mat int32] -> (idx, (code, affine))
-        device views, and with `origin` (int [n][3], --crop) the origin view as a third item.
-        With `mat` (int [n][4], --augment rotate / scale) the second item is (code, affine, mat)."""
+        [idx int64 | affine fp32 | code int32 | origin int32 | mat int32 | field int32] ->
+        (idx, (code, affine)) device views, and with `origin` (int [n][3], --crop) the origin view
+        as a third item.  With `mat` (int [n][4], --augment rotate / scale) the second item is
+        (code, affine, mat); with `field` (int [n][N][N][2], --augment elastic) it is (code, affine,
+        mat or None, field): the field rides at the end, every other view keeps its offset."""
         n = len(sorted_idx)
         af = np.ascontiguousarray(affine, dtype=np.float32) if affine is not None else np.empty(0, np.float32)
         parts = [sorted_idx.view(np.uint8), af.reshape(-1).view(np.uint8),
@@ -159,6 +177,9 @@ class DeviceFeeder:
             parts.append(np.ascontiguousarray(origin, dtype=np.int32).reshape(-1).view(np.uint8))
         if mat is not None:
             parts.append(np.ascontiguousarray(mat, dtype=np.int32).reshape(-1).view(np.uint8))
+        if field is not None:
+            field = np.ascontiguousarray(field, dtype=np.int32)
+            parts.append(field.reshape(-1).view(np.uint8))
         buf = torch.from_numpy(np.concatenate(parts)).to(self.device, non_blocking=True)
         na = parts[1].size
         ii = buf[:8 * n].view(torch.int64)
@@ -166,7 +187,11 @@ class DeviceFeeder:
         cd = buf[8 * n + na:8 * n + na + 4 * n].view(torch.int32)
         at = 8 * n + na + 4 * n
         no = 12 * n if origin is not None else 0
-        dev = (cd, af) if mat is None else (cd, af, buf[at + no:at + no + 16 * n].view(torch.int32).view(n, 4))
+        nm = 16 * n if mat is not None else 0
+        dev = (cd, af) if mat is None else (cd, af, buf[at + no:at + no + nm].view(torch.int32).view(n, 4))
+        if field is not None:
+            dev = dev[:2] + (dev[2] if mat is not None else None,
+                             buf[at + no + nm:at + no + nm + field.nbytes].view(torch.int32).view(field.shape))
         if origin is None:
             return ii, dev
         return ii, dev, buf[at:at + no].view(torch.int32).view(n, 3)
@@ -180,7 +205,8 @@ class DeviceFeeder:
         is the patches at the origins, cropped first and then augmented.  Either tuple may end in
         the warp matrices `mat` (--augment rotate / scale): the batch is then resampled through
         them straight from the stored samples (augment.warp_torch; the backend's gather kernel
-        for a ResidentBatch)."""
+        for a ResidentBatch).  With --augment elastic the tuples are (code, affine, mat or None,
+        field) and (code, affine, origin, mat or None, field) (augment.elastic_torch)."""
         if aug is None:
             if self.patch is not None:
                 raise ValueError("a cropping feeder needs the per-step origins (aug)")
@@ -189,33 +215,40 @@ class DeviceFeeder:
         drawn = aug(si)
         if self.patch is not None:
             return self._get_crop(si, lazy, *drawn)
-        code, affine, mat = drawn if len(drawn) > 2 else tuple(drawn) + (None,)
+        code, affine, mat, field = (tuple(drawn) + (None, None))[:4]
         if self.resident:
-            ii, dev = self._upload(si, code, affine, mat=mat)
+            ii, dev = self._upload(si, code, affine, mat=mat, field=field)
             if lazy:
-                return ResidentBatch(self.x, self.y, ii, dev), None
+                return ResidentBatch(self.x, self.y, ii, dev, elastic_cell=self.elastic_cell), None
             x, y = self.x.index_select(0, ii), self.y.index_select(0, ii)
-            return apply_torch(x, y, code, affine) if mat is None else warp_batch(x, y, None, code, affine, mat)
-        x, y = self._get(idx, False)
+        else:
+            x, y = self._get(idx, False)
+        if field is not None:
+            return elastic_batch(x, y, None, code, affine, mat, field, self.elastic_cell)
         return apply_torch(x, y, code, affine) if mat is None else warp_batch(x, y, None, code, affine, mat)
 
-    def _get_crop(self, si: np.ndarray, lazy: bool, code, affine, origin, mat=None):
+    def _get_crop(self, si: np.ndarray, lazy: bool, code, affine, origin, mat=None, field=None):
         origin = np.ascontiguousarray(origin, dtype=np.int32).reshape(len(si), 3)
         if self.resident:
-            ii, dev, org = self._upload(si, code, affine, origin, mat)
+            ii, dev, org = self._upload(si, code, affine, origin, mat, field)
             if lazy:
-                return ResidentBatch(self.x, self.y, ii, dev, (org, self.patch)), None
+                return ResidentBatch(self.x, self.y, ii, dev, (org, self.patch), self.elastic_cell), None
             x, y = self.x.index_select(0, ii), self.y.index_select(0, ii)
+            if field is not None:
+                return elastic_batch(x, y, (origin, self.patch), code, affine, mat, field, self.elastic_cell)
             if mat is not None:
                 return warp_batch(x, y, (origin, self.patch), code, affine, mat)
             return apply_torch(*crop_torch(x, y, origin, self.patch), code, affine)
-        if mat is not None:
+        if mat is not None or field is not None:
             # streamed and warped: the taps leave the patch rectangle, so the host resamples the
             # whole stored samples and only the patches are copied to the device
             ld = self.loaders[0]
             x = torch.from_numpy(np.ascontiguousarray(ld.x[si], dtype=np.float32))
             y = torch.from_numpy(np.ascontiguousarray(ld.y[si], dtype=np.float32))
-            x, y = warp_batch(x, y, (origin, self.patch), code, affine, mat)
+            if field is not None:
+                x, y = elastic_batch(x, y, (origin, self.patch), code, affine, mat, field, self.elastic_cell)
+            else:
+                x, y = warp_batch(x, y, (origin, self.patch), code, affine, mat)
             return x.to(self.device), y.to(self.device)
         # streamed: the host copies each sample's patch into the patch-sized staging buffers
         return apply_torch(*self._get(si, False, origin), code, affine)

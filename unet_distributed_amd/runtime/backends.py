@@ -285,7 +285,10 @@ class NativeBackend:
         self._pp_thr = None
         e.set_loss_scale(grad_scale)
         if hasattr(x, "x_all"):
-            if getattr(x, "crop", None) is not None:
+            if getattr(x, "aug", None) is not None and len(x.aug) > 3:      # --augment elastic: the field's cell
+                e.load_indexed(x.x_all, x.y_all, x.idx, aug=x.aug, crop=getattr(x, "crop", None),
+                               elastic_cell=x.elastic_cell)
+            elif getattr(x, "crop", None) is not None:
                 e.load_indexed(x.x_all, x.y_all, x.idx, aug=x.aug, crop=x.crop)
             elif getattr(x, "aug", None) is not None:
                 e.load_indexed(x.x_all, x.y_all, x.idx, aug=x.aug)

@@ -38,6 +38,12 @@ def has_mat(aug) -> bool:
     return aug is not None and len(aug) > 2 and aug[2] is not None
 
 
+def has_field(aug) -> bool:
+    """Whether the augmentation parameters `aug` end in an elastic field: (code, affine, mat or
+    None, field)."""
+    return aug is not None and len(aug) > 3 and aug[3] is not None
+
+
 # cap of an executor's surf_dist scratch: the field is 8 bytes per (voxel, class) of a sample
 # group, 384 MiB for K = 3 at b1024 128x128.  256 MiB keeps the 3D b8 128^3 K = 1 batch
 # (128 MiB) and the 2D b1024 K = 1 batch (128 MiB) in one group and splits only the
@@ -265,7 +271,7 @@ class ExecutorBase:
         raise NotImplementedError
 
     def load_indexed(self, x_all: torch.Tensor, y_all: torch.Tensor, idx: torch.Tensor, stream=None, aug=None,
-                     crop=None):
+                     crop=None, elastic_cell: int = 32):
         """Batch = samples `idx` (device int64) of the HBM-resident dataset, gathered
         and cast straight into the (padded) input and the target (one launch).  `aug`:
         optional (code int32 [B], affine float32 [B][Cin][2] or None) on the device
@@ -275,25 +281,33 @@ class ExecutorBase:
         launch reads each sample's patch at its origin, then transforms it (kernels/gather_crop.h).
         An `aug` of three items (code or None, affine or None, mat int32 [B][4]) resamples the
         patch -- the whole sample without `crop` -- through each sample's matrix in the same
-        launch (kernels/gather_warp.h)."""
+        launch (kernels/gather_warp.h).  An `aug` of four items (code or None, affine or None, mat or
+        None, field int32 [B][N][N][2]) adds the elastic displacement of each sample's field to
+        the warp's source coordinates (kernels/gather_elastic.h): `elastic_cell` is the side S of a
+        lattice cell in patch pixels and N = ((H - 1) >> log2 S) + 3."""
         if aug is None and crop is None:
             return self._load_plain(x_all, y_all, idx, stream)
         self._check_indexed(x_all, y_all, idx)
         assert y_all.dtype == torch.float32
-        name, ptrs, ints = self._gather_args(x_all, y_all, idx, aug, crop)
+        name, ptrs, ints = self._gather_args(x_all, y_all, idx, aug, crop, elastic_cell)
         self.C.generic(self._op(name), ptrs, ints, [], native.stream_handle(stream), self.dt_id)
 
-    def _gather_args(self, x_all, y_all, idx, aug, crop):
-        """(op name, ptrs, ints) of the gather_batch_aug / _crop / _warp launch (bindings.cpp)
+    def _gather_args(self, x_all, y_all, idx, aug, crop, elastic_cell: int = 32):
+        """(op name, ptrs, ints) of the gather_batch_aug / _crop / _warp / _elastic launch (bindings.cpp)
         that loads the batch from the resident dataset [N, (Ds,) Hs, Ws, Cin]: `aug` = (code or
         None, affine or None[, mat int32 [B][4] or None]) or None, `crop` = (origin int32 [B][3],
         patch dims (D, H, W)) or None.  With `mat` it is the warp, whose patch without `crop` is
         the executor's input at origin 0, which the stored sample must hold; else with `crop`
-        the crop; else the augmenting gather of whole samples, which needs its codes."""
+        the crop; else the augmenting gather of whole samples, which needs its codes.  An `aug` of
+        four items ends in the elastic field (int32 [B][N][N][2], cells of `elastic_cell` patch
+        pixels) and selects the elastic op, whose `mat` may be None."""
         code, affine = aug[:2] if aug is not None else (None, None)
         mat = aug[2] if has_mat(aug) else None
-        name = "gather_batch_warp" if mat is not None else "gather_batch_crop" if crop is not None \
-            else "gather_batch_aug"
+        field = aug[3] if has_field(aug) else None
+        if aug is not None and len(aug) > 3 and field is None:
+            raise ValueError("an augmentation of four items ends in the elastic field")
+        name = "gather_batch_elastic" if field is not None else "gather_batch_warp" if mat is not None \
+            else "gather_batch_crop" if crop is not None else "gather_batch_aug"
         B, cin, dev = self.B, self.spec.in_channels, x_all.device
         stored = (x_all.shape[1] if x_all.dim() == 5 else 1, x_all.shape[-3], x_all.shape[-2])
         origin, patch = crop if crop is not None else (None, self.sdims(1))
@@ -302,9 +316,18 @@ class ExecutorBase:
             assert stored == tuple(self.sdims(1))
         elif patch != tuple(self.sdims(1)):
             raise ValueError("crop patch %r: the executor's input is %r" % (patch, tuple(self.sdims(1))))
-        if mat is not None:
+        if mat is not None or field is not None:
             if any(t > s for t, s in zip(patch, stored)):
                 raise ValueError("the executor's input %r exceeds the stored sample %r" % (patch, stored))
+        if field is not None:
+            from ..data.augment import elastic_log2, elastic_nodes
+            slog = elastic_log2(elastic_cell)
+            N = elastic_nodes(patch[1], elastic_cell)
+            if field.dtype != torch.int32 or tuple(field.shape) != (B, N, N, 2) or field.device != dev \
+                    or not field.is_contiguous():
+                raise ValueError("elastic field: a contiguous int32 [%d][%d][%d][2] tensor on %s (cell %d)"
+                                 % (B, N, N, dev, elastic_cell))
+        if mat is not None:
             if mat.dtype != torch.int32 or tuple(mat.shape) != (B, 4) or mat.device != dev or not mat.is_contiguous():
                 raise ValueError("warp matrices: a contiguous int32 [%d][4] tensor on %s" % (B, dev))
         if (origin is not None or name == "gather_batch_crop") and (
@@ -318,9 +341,13 @@ class ExecutorBase:
                                    or affine.device != dev or not affine.is_contiguous()):
             raise ValueError("augmentation affine: a contiguous float32 [%d][%d][2] tensor on %s" % (B, cin, dev))
         whole = name == "gather_batch_aug"
-        ptrs = ([x_all, y_all, idx] + ([] if whole else [origin]) + [code] + ([] if mat is None else [mat])
-                + [affine, self.bufs["x"], self.target])
-        ints = [B] + list(stored) + ([] if whole else list(patch)) + [cin, self.cpad, self.K]
+        if field is not None:
+            ptrs = [x_all, y_all, idx, origin, code, mat, affine, field, self.bufs["x"], self.target]
+        else:
+            ptrs = ([x_all, y_all, idx] + ([] if whole else [origin]) + [code] + ([] if mat is None else [mat])
+                    + [affine, self.bufs["x"], self.target])
+        ints = [B] + list(stored) + ([] if whole else list(patch)) + [cin, self.cpad, self.K] + (
+            [] if field is None else [slog])
         return name, [0 if t is None else _ptr(t) for t in ptrs], ints
 
     # ------------------------------------------------------------------ evaluation

@@ -132,6 +132,12 @@ def _generic_write_spans(kind: str, p: List[int], ints: List[int]) -> List[Tuple
         B, _, _, _, D, H, W, _, cpad, K = ints[:10]
         eb = 4 if kind.startswith("f32") else 2
         return [(p[7], B * D * H * W * cpad * eb), (p[8], B * D * H * W * K * eb)]
+    # elastic batch gather (the warp's ints and the cell's log2; one more pointer, the field, after
+    # the affine)
+    if kind in ("gather_batch_elastic", "f32_gather_batch_elastic") and len(p) > 9 and len(ints) >= 11:
+        B, _, _, _, D, H, W, _, cpad, K = ints[:10]
+        eb = 4 if kind.startswith("f32") else 2
+        return [(p[8], B * D * H * W * cpad * eb), (p[9], B * D * H * W * K * eb)]
     # test-time augmentation: the fp32 accumulator (N, D, H, W, K in ints); the finish (total
     # elements in ints) rewrites prob and writes one row of 4 floats per block and the 4 sums
     if kind == "tta_acc" and len(p) > 1 and len(ints) >= 5:
@@ -245,6 +251,8 @@ def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], Li
         return [q for q in _sel(p, [0, 1, 2, 3, 4, 5]) if q], _sel(p, [6, 7])
     if kind in ("gather_batch_warp", "f32_gather_batch_warp"):
         return [q for q in _sel(p, [0, 1, 2, 3, 4, 5, 6]) if q], _sel(p, [7, 8])
+    if kind in ("gather_batch_elastic", "f32_gather_batch_elastic"):
+        return [q for q in _sel(p, [0, 1, 2, 3, 4, 5, 6, 7]) if q], _sel(p, [8, 9])
     if kind == "tta_acc":                # (write mode reads no element of the accumulator)
         return _sel(p, [0, 1] if len(ints) > 6 and ints[6] else [0]), _sel(p, [1])
     if kind in ("tta_finish", "f32_tta_finish"):

@@ -245,20 +245,25 @@ class Trainer:
             self.aug_ranges["rotate_deg"] = [-float(cfg.augment_rotate), float(cfg.augment_rotate)]
         if "scale" in names:
             self.aug_ranges["scale"] = [1.0 / (1.0 + cfg.augment_scale), 1.0 + cfg.augment_scale]
+        if "elastic" in names:
+            self.aug_ranges["elastic"] = {"sigma_px": float(cfg.augment_elastic), "cell": int(cfg.augment_elastic_cell)}
         self.sampler = datasets.EpochSampler(len(self.x_train), cfg.batch_size, self.rank, self.world, cfg.seed)
         self.num_batches = self.sampler.num_batches
         self.feeder = DeviceFeeder(self.x_train, self.y_train, self.per_rank, self.device,
-                                   threads=min(cfg.num_threads, 16), mode=cfg.data_on_device, patch=self.crop_patch)
+                                   threads=min(cfg.num_threads, 16), mode=cfg.data_on_device, patch=self.crop_patch,
+                                   elastic_cell=cfg.augment_elastic_cell)
         if self.is_chief:
             print("Training data: %s" % ("resident in device memory" if self.feeder.resident
                                          else "streamed from host (pinned, double-buffered)"))
             if cfg.augment:
                 names = parse_augment(cfg.augment)
-                print("Training augmentation: %s%s%s%s" % (
+                print("Training augmentation: %s%s%s%s%s" % (
                     ", ".join(names), " (amplitude %g)" % cfg.augment_intensity if "intensity" in names else "",
                     " (rotate +-%g deg)" % cfg.augment_rotate if "rotate" in names else "",
                     " (scale %.4g..%.4g)" % (1.0 / (1.0 + cfg.augment_scale), 1.0 + cfg.augment_scale)
-                    if "scale" in names else ""))
+                    if "scale" in names else "",
+                    " (elastic sigma %g px, cell %d)" % (cfg.augment_elastic, cfg.augment_elastic_cell)
+                    if "elastic" in names else ""))
             if self.crop_mode:
                 print("Training patches: %s of %s, %s" % (
                     " x ".join(map(str, model)), " x ".join(map(str, stored)),
@@ -531,7 +536,7 @@ class Trainer:
                 m["images_per_sec"] = imgs_since / max(dt, 1e-9)
                 m["lr"] = learning_rate(cfg, step)
                 m["percent_complete"] = 100.0 * step / total
-                if getattr(self, "aug_ranges", None):   # --augment rotate / scale: the ranges the matrices are drawn from
+                if getattr(self, "aug_ranges", None):   # --augment rotate / scale / elastic: the ranges the matrices and fields are drawn from
                     m["augment"] = dict(self.aug_ranges)
                 imgs = None
                 if self.is_chief and self.log.events is not None and hasattr(self.backend, "summary_images"):
