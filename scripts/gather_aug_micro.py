@@ -1,4 +1,4 @@
-"""Per-launch time of the augmenting batch gather (gather_aug.h) at the bench shape -- batch
+"""Per-launch time of the augmenting batch gather (gather.h) at the bench shape -- batch
 1024 of 128x128x4, one target channel, bf16 -- next to the plain gather_batch kernel on the
 same buffers in the same process, cases interleaved and repeated (profiles/r9_augment.md).
 The batch is drawn (sorted indices, as the feeder sends them) from a resident set four

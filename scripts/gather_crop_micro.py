@@ -1,6 +1,6 @@
-"""Per-launch time of the cropping batch gather (gather_crop.h) at the bench shape -- batch
+"""Per-launch time of the cropping batch gather (gather.h) at the bench shape -- batch
 1024 of 128x128x4 patches, one target channel, bf16 -- next to the augmenting gather
-(gather_aug.h, the yardstick) on a 128x128 resident set in the same process, cases
+(gather.h, the yardstick) on a 128x128 resident set in the same process, cases
 interleaved and repeated (profiles/r15_crop.md).  The 128x128 set is four times the batch
 (1.3 GB), the 240x240 set twice the batch (2.4 GB); the batches are sorted indices, as the
 feeder sends them, and the outputs rotate over four buffer pairs, so no pass re-reads the

@@ -1,6 +1,6 @@
-"""Per-launch time of the elastic batch gather (gather_elastic.h) at the bench shape -- batch 1024
-of 128x128x4 patches out of 240x240 slices, bf16 -- next to the resampling gather (gather_warp.h)
-and the cropping gather (gather_crop.h, the yardstick) on the same resident set in the same
+"""Per-launch time of the elastic batch gather (gather_resample.h) at the bench shape -- batch 1024
+of 128x128x4 patches out of 240x240 slices, bf16 -- next to the resampling gather (gather_resample.h)
+and the cropping gather (gather.h, the yardstick) on the same resident set in the same
 process, cases interleaved and repeated (profiles/r19_elastic.md).  The 240x240 set is twice the
 batch (2.4 GB); the batches are sorted indices, as the feeder sends them, and the outputs rotate
 over four buffer pairs, so no pass re-reads the 256 MiB Infinity Cache.  Matrices are

@@ -1,6 +1,6 @@
-"""Per-launch time of the resampling batch gather (gather_warp.h) at the bench shape -- batch
+"""Per-launch time of the resampling batch gather (gather_resample.h) at the bench shape -- batch
 1024 of 128x128x4 patches out of 240x240 slices, bf16 -- next to the cropping gather
-(gather_crop.h, the yardstick) on the same resident set in the same process, cases interleaved
+(gather.h, the yardstick) on the same resident set in the same process, cases interleaved
 and repeated (profiles/r16_warp.md).  The 240x240 set is twice the batch (2.4 GB); the batches
 are sorted indices, as the feeder sends them, and the outputs rotate over four buffer pairs, so
 no pass re-reads the 256 MiB Infinity Cache.  Cases: the identity matrix (the crop's pixels, four

@@ -1,5 +1,5 @@
 """Training-time augmentation on the GPU: the augmenting batch gather
-(csrc/kernels/gather_aug.h, ops gather_batch_aug / f32_gather_batch_aug) against
+(csrc/kernels/gather.h, ops gather_batch_aug / f32_gather_batch_aug) against
 data/augment.py's apply_torch on the plain gather's output -- bit for bit, the geometric
 transform is a permutation -- the intensity affine against float64 within one rounding to
 the storage type, and the executors' load_indexed(aug=...) against pre-augmented tensors.

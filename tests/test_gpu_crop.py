@@ -1,4 +1,4 @@
-"""Patch-sampled training on the GPU: the cropping batch gather (csrc/kernels/gather_crop.h,
+"""Patch-sampled training on the GPU: the cropping batch gather (csrc/kernels/gather.h,
 ops gather_batch_crop / f32_gather_batch_crop) against the definition in plain torch --
 apply_torch(crop_torch(index_select)) cast to the storage type, bit for bit: cropping and the
 geometric transform only move pixels -- the intensity affine against float64 within one

@@ -1,4 +1,4 @@
-"""Elastic augmentation on the GPU: the elastic batch gather (csrc/kernels/gather_elastic.h, ops
+"""Elastic augmentation on the GPU: the elastic batch gather (csrc/kernels/gather_resample.h, ops
 gather_batch_elastic / f32_gather_batch_elastic) against the definition in plain torch --
 apply_torch(elastic_torch(index_select)) cast to the storage type, bit for bit: the geometry and
 the displacement are integer and every fp32 product and sum rounds on its own in both -- the
@@ -345,7 +345,7 @@ def test_fields_matrices_and_origins_outside_their_ranges_are_clamped(cuda_dev, 
 
 @pytest.mark.parametrize("tname", ["bf16", "fp32"])
 def test_bad_shapes_and_missing_pointers_are_refused(cuda_dev, tname):
-    """gather_elastic_check in the bindings: nothing is launched, the outputs keep their NaNs."""
+    """gather_check in the bindings: nothing is launched, the outputs keep their NaNs."""
     dev = cuda_dev
     dt, op, _, _, dt_id, _ = TYPES[tname]
     x_all, y_all = dataset((40, 48), 4, 2)

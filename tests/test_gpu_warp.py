@@ -1,5 +1,5 @@
 """Rotate / scale augmentation on the GPU: the resampling batch gather (csrc/kernels/
-gather_warp.h, ops gather_batch_warp / f32_gather_batch_warp) against the definition in plain
+gather_resample.h, ops gather_batch_warp / f32_gather_batch_warp) against the definition in plain
 torch -- apply_torch(warp_torch(index_select)) cast to the storage type, bit for bit: the
 geometry is integer and every fp32 product and sum rounds on its own in both -- the intensity
 affine against float64 within one rounding, matrices and origins outside their ranges against
@@ -305,7 +305,7 @@ def test_matrices_and_origins_outside_their_ranges_are_clamped(cuda_dev, tname):
 
 @pytest.mark.parametrize("tname", ["bf16", "fp32"])
 def test_bad_shapes_and_missing_pointers_are_refused(cuda_dev, tname):
-    """gather_warp_check in the bindings: nothing is launched, the outputs keep their NaNs."""
+    """gather_check in the bindings: nothing is launched, the outputs keep their NaNs."""
     dev = cuda_dev
     dt, op, _, dt_id, _ = TYPES[tname]
     x_all, y_all = dataset((40, 48), 4, 2)

@@ -1,5 +1,5 @@
 """LDS bank-conflict model (tools/lds_bank_model.py) of the augmenting batch gather's tile
-transpose (csrc/kernels/gather_aug.h): the padded row pitches make the row writes and the
+transpose (csrc/kernels/gather.h): the padded row pitches make the row writes and the
 transposed reads conflict-free where the unpadded tile is a 32- / 16-way conflict."""
 import os
 import sys

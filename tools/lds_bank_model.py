@@ -206,7 +206,7 @@ def check_tconv_epi(W, padded=False):
 
 
 # ---------------------------------------------------------------- gather_aug tile transpose
-# gather_aug.h gather_aug_tile_kernel: 32 x 32 pixel tile, a pixel is nw dwords (2: Cpad 4 in
+# gather.h gather_copy_tile_kernel: 32 x 32 pixel tile, a pixel is nw dwords (2: Cpad 4 in
 # 16 bits; 4: Cpad 8 in 16 bits or Cpad 4 in fp32; 8: Cpad 8 in fp32), rows of 32 nw + pad
 # dwords.  Lane (r, c) = (tid >> 5, tid & 31) writes pixel [r + 8 i][c] and reads back
 # [c][r + 8 i]; 8-byte accesses for nw = 2, 16-byte pieces otherwise.  The target planes are

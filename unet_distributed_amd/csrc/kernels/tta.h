@@ -6,12 +6,12 @@
 //   target TT   [N][D][H][W][K]   (TT: the build's 16-bit type, or float for the fp32 executor)
 //
 // tta_acc: acc[n][o][k] (=|+=) prob[n][f_code(o)][k] for ONE code, uniform over the launch,
-// with f the source map of gather_aug.h: output pixel (d, h, w) reads source pixel
+// with f the source map of gather.h: output pixel (d, h, w) reads source pixel
 //   d' = FD ? D-1-d : d;   (a, b) = T ? (w, h) : (h, w);   h' = FH ? H-1-a : a;   w' = FW ? W-1-b : b
 // (bits: 0 FW, 1 FH, 2 T, 3 FD).  The caller passes the inverse of the code its gather used.
 // In write mode no element of acc is read.
 //
-// Geometry (gather_aug.h's): a workgroup of 256 lanes owns 1024 pixels of one (sample, slice),
+// Geometry (gather.h's): a workgroup of 256 lanes owns 1024 pixels of one (sample, slice),
 // i.e. 1024 K floats, 4 K per lane.  prob and acc are addressed as flat float runs -- lane
 // `tid` takes floats tid, tid + 256, ... of the workgroup's rows, so a wave's access is 256
 // contiguous bytes whatever K is (a K = 3 pixel is 12 bytes and is never addressed as a vector).

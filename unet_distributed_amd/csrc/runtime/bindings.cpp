@@ -283,10 +283,7 @@ F32Wgrad f32_wgrad_params(const py::dict& d) {
   X(colsum_launch) \
   X(cast_input_launch) \
   X(gather_batch_launch) \
-  X(gather_batch_aug_launch) \
-  X(gather_batch_crop_launch) \
-  X(gather_batch_warp_launch) \
-  X(gather_batch_elastic_launch) \
+  X(gather_launch) \
   X(maxpool2_fwd_launch) \
   X(norm_pool_launch) \
   X(maxpool2_bwd_launch) \
@@ -372,104 +369,47 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
     if (K > 1 && I[0] * I[1] * K >= (1LL << 31)) throw std::invalid_argument("gather_batch: B P K >= 2^31");
     return [=](hipStream_t s) { return A->gather_batch_launch(xa, ya, ix, B, P_, cin, cpad, xb, tb, K, s); };
   }
-  if (kind == "gather_batch_aug" || kind == "f32_gather_batch_aug") {
-    // ptrs: x_all, y_all, idx (int64), code (int32 [B]), affine (fp32 [B][Cin][2] or 0), xb, tb
-    //       (gather_batch_aug: the 16-bit type, f32_gather_batch_aug: fp32)
-    // ints: B, D, H, W, Cin, Cpad, K
-    need(7, 7, 0);
-    check_msg(gather_aug_check(I[0], I[1], I[2], I[3], I[4], I[5], I[6]));
-    const float *xa = (const float*)vp(0), *ya = (const float*)vp(1);
-    const long long* ix = (const long long*)vp(2);
-    const int* code = (const int*)vp(3);
-    const float* aff = (const float*)vp(4);
-    void *xb = vp(5), *tb = vp(6);
-    if (!xa || !ya || !ix || !code || !xb || !tb)
-      throw std::invalid_argument("gather_batch_aug: x_all / y_all / idx / code / xb / tb required");
-    int B = I[0], D = I[1], H = I[2], W = I[3], cin = I[4], cpad = I[5], K = I[6];
-    if (kind == "f32_gather_batch_aug")
-      return [=](hipStream_t s) {
-        return unet::f32_gather_batch_aug_launch(xa, ya, ix, code, aff, B, D, H, W, cin, cpad, K, (float*)xb,
-                                                 (float*)tb, s);
-      };
-    return [=](hipStream_t s) {
-      return A->gather_batch_aug_launch(xa, ya, ix, code, aff, B, D, H, W, cin, cpad, K, xb, tb, s);
-    };
-  }
-  if (kind == "gather_batch_crop" || kind == "f32_gather_batch_crop") {
-    // ptrs: x_all, y_all, idx (int64), origin (int32 [B][3]), code (int32 [B] or 0), affine (fp32
-    //       [B][Cin][2] or 0), xb, tb (gather_batch_crop: the 16-bit type, f32_gather_batch_crop: fp32)
-    // ints: B, Ds, Hs, Ws, D, H, W, Cin, Cpad, K
-    need(8, 10, 0);
-    check_msg(gather_crop_check(I[0], I[1], I[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9]));
-    const float *xa = (const float*)vp(0), *ya = (const float*)vp(1);
-    const long long* ix = (const long long*)vp(2);
-    const int *org = (const int*)vp(3), *code = (const int*)vp(4);
-    const float* aff = (const float*)vp(5);
-    void *xb = vp(6), *tb = vp(7);
-    if (!xa || !ya || !ix || !org || !xb || !tb)
-      throw std::invalid_argument("gather_batch_crop: x_all / y_all / idx / origin / xb / tb required");
-    int B = I[0], Ds = I[1], Hs = I[2], Ws = I[3], D = I[4], H = I[5], W = I[6], cin = I[7], cpad = I[8], K = I[9];
-    if (kind == "f32_gather_batch_crop")
-      return [=](hipStream_t s) {
-        return unet::f32_gather_batch_crop_launch(xa, ya, ix, org, code, aff, B, Ds, Hs, Ws, D, H, W, cin, cpad, K,
-                                                  (float*)xb, (float*)tb, s);
-      };
-    return [=](hipStream_t s) {
-      return A->gather_batch_crop_launch(xa, ya, ix, org, code, aff, B, Ds, Hs, Ws, D, H, W, cin, cpad, K, xb, tb, s);
-    };
-  }
-  if (kind == "gather_batch_warp" || kind == "f32_gather_batch_warp") {
-    // ptrs: x_all, y_all, idx (int64), origin (int32 [B][3] or 0), code (int32 [B] or 0), mat (int32
-    //       [B][4], Q16), affine (fp32 [B][Cin][2] or 0), xb, tb (gather_batch_warp: the 16-bit type,
-    //       f32_gather_batch_warp: fp32)
-    // ints: B, Ds, Hs, Ws, D, H, W, Cin, Cpad, K
-    need(9, 10, 0);
-    check_msg(gather_warp_check(I[0], I[1], I[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9]));
-    const float *xa = (const float*)vp(0), *ya = (const float*)vp(1);
-    const long long* ix = (const long long*)vp(2);
-    const int *org = (const int*)vp(3), *code = (const int*)vp(4), *mat = (const int*)vp(5);
-    const float* aff = (const float*)vp(6);
-    void *xb = vp(7), *tb = vp(8);
-    if (!xa || !ya || !ix || !mat || !xb || !tb)
-      throw std::invalid_argument("gather_batch_warp: x_all / y_all / idx / mat / xb / tb required");
-    int B = I[0], Ds = I[1], Hs = I[2], Ws = I[3], D = I[4], H = I[5], W = I[6], cin = I[7], cpad = I[8], K = I[9];
-    if (kind == "f32_gather_batch_warp")
-      return [=](hipStream_t s) {
-        return unet::f32_gather_batch_warp_launch(xa, ya, ix, org, code, mat, aff, B, Ds, Hs, Ws, D, H, W, cin, cpad,
-                                                  K, (float*)xb, (float*)tb, s);
-      };
-    return [=](hipStream_t s) {
-      return A->gather_batch_warp_launch(xa, ya, ix, org, code, mat, aff, B, Ds, Hs, Ws, D, H, W, cin, cpad, K, xb, tb,
-                                         s);
-    };
-  }
-  if (kind == "gather_batch_elastic" || kind == "f32_gather_batch_elastic") {
-    // ptrs: x_all, y_all, idx (int64), origin (int32 [B][3] or 0), code (int32 [B] or 0), mat (int32
-    //       [B][4], Q16, or 0 = the identity), affine (fp32 [B][Cin][2] or 0), field (int32
-    //       [B][N][N][2], N = ((H - 1) >> s) + 3), xb, tb (gather_batch_elastic: the 16-bit type,
-    //       f32_gather_batch_elastic: fp32)
-    // ints: B, Ds, Hs, Ws, D, H, W, Cin, Cpad, K, s (log2 of the cell side)
-    need(10, 11, 0);
-    check_msg(gather_elastic_check(I[0], I[1], I[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9], I[10]));
-    const float *xa = (const float*)vp(0), *ya = (const float*)vp(1);
-    const long long* ix = (const long long*)vp(2);
-    const int *org = (const int*)vp(3), *code = (const int*)vp(4), *mat = (const int*)vp(5);
-    const float* aff = (const float*)vp(6);
-    const int* fld = (const int*)vp(7);
-    void *xb = vp(8), *tb = vp(9);
-    if (!xa || !ya || !ix || !fld || !xb || !tb)
-      throw std::invalid_argument("gather_batch_elastic: x_all / y_all / idx / field / xb / tb required");
-    int B = I[0], Ds = I[1], Hs = I[2], Ws = I[3], D = I[4], H = I[5], W = I[6], cin = I[7], cpad = I[8], K = I[9];
-    int sl = I[10];
-    if (kind == "f32_gather_batch_elastic")
-      return [=](hipStream_t s) {
-        return unet::f32_gather_batch_elastic_launch(xa, ya, ix, org, code, mat, aff, fld, B, Ds, Hs, Ws, D, H, W, cin,
-                                                     cpad, K, sl, (float*)xb, (float*)tb, s);
-      };
-    return [=](hipStream_t s) {
-      return A->gather_batch_elastic_launch(xa, ya, ix, org, code, mat, aff, fld, B, Ds, Hs, Ws, D, H, W, cin, cpad, K,
-                                            sl, xb, tb, s);
-    };
+  // the batch gathers (gather.h, gather_resample.h): gather_batch_<op> writes the 16-bit type,
+  // f32_gather_batch_<op> fp32.  ptrs: x_all, y_all, idx (int64 [B]), the op's own, xb, tb
+  //   op       its own ptrs                                        ints
+  //   aug      code, affine                                        B, D, H, W, Cin, Cpad, K
+  //   crop     origin, code, affine                                B, Ds, Hs, Ws, D, H, W, Cin, Cpad, K
+  //   warp     origin, code, mat, affine                           the same
+  //   elastic  origin, code, mat, affine, field                    the same, s (log2 of the cell side)
+  // origin int32 [B][3], code int32 [B], mat int32 [B][4] (Q16), affine fp32 [B][Cin][2], field int32
+  // [B][N][N][2], N = ((H - 1) >> s) + 3.  Each may be 0 (origin, code = 0; mat = the identity; no
+  // affine) except the one named last: code for aug, origin for crop, mat for warp, field for elastic
+  struct GatherRow {
+    const char* name;
+    GatherOp op;
+    int origin, code, mat, affine, field, xb;   // positions in ptrs (-1: not taken); tb follows xb
+    int patch;                                  // position of the patch's D in ints
+    const char* required;
+  };
+  static const GatherRow kGather[] = {{"gather_batch_aug", GatherOp::aug, -1, 3, -1, 4, -1, 5, 1, "code"},
+                                      {"gather_batch_crop", GatherOp::crop, 3, 4, -1, 5, -1, 6, 4, "origin"},
+                                      {"gather_batch_warp", GatherOp::warp, 3, 4, 5, 6, -1, 7, 4, "mat"},
+                                      {"gather_batch_elastic", GatherOp::elastic, 3, 4, 5, 6, 7, 8, 4, "field"}};
+  const bool f32 = kind.rfind("f32_", 0) == 0;
+  for (const GatherRow& g : kGather) {
+    if (kind.compare(f32 ? 4 : 0, std::string::npos, g.name) != 0) continue;
+    const GatherOp op = g.op;
+    need(g.xb + 2, g.patch + 6 + (op == GatherOp::elastic), 0);
+    auto at = [&](int i) { return i < 0 ? nullptr : vp(i); };
+    GatherArgs a{};
+    a.x_all = (const float*)vp(0), a.y_all = (const float*)vp(1), a.idx = (const long long*)vp(2);
+    a.origin = (const int*)at(g.origin), a.code = (const int*)at(g.code), a.mat = (const int*)at(g.mat);
+    a.affine = (const float*)at(g.affine), a.field = (const int*)at(g.field);
+    const long long* J = I.data() + g.patch;
+    a.B = I[0], a.D = J[0], a.H = J[1], a.W = J[2], a.Cin = J[3], a.Cpad = J[4], a.K = J[5];
+    if (g.patch == 4) a.Ds = I[1], a.Hs = I[2], a.Ws = I[3];
+    if (op == GatherOp::elastic) a.s = J[6];
+    check_msg(gather_check(op, a));
+    void *xb = vp(g.xb), *tb = vp(g.xb + 1);
+    if (!a.x_all || !a.y_all || !a.idx || !gather_required(op, a) || !xb || !tb)
+      throw std::invalid_argument(std::string(g.name) + ": x_all / y_all / idx / " + g.required + " / xb / tb required");
+    if (f32) return [=](hipStream_t s) { return unet::f32_gather_launch(op, a, xb, tb, s); };
+    return [=](hipStream_t s) { return A->gather_launch(op, a, xb, tb, s); };
   }
   if (kind == "pool_fwd") {
     // ptrs: x, y[, code]

@@ -25,41 +25,20 @@ hipError_t cast_input_launch(const float* x, int P, int Cin, int Cpad, void* y, 
 // (K target channels per pixel, 1..4)
 hipError_t gather_batch_launch(const float* x_all, const float* y_all, const long long* idx, int B, int P, int Cin,
                                int Cpad, void* xb, void* tb, int K, hipStream_t s);
-// gather_batch with a per-sample geometric transform (code int32 [B]: bit 0 flip W, 1 flip H,
-// 2 swap H and W, 3 flip D) and an optional per-channel affine (fp32 [B][Cin][2] = {scale,
-// shift}, may be null) on the image (gather_aug.h); H == W
-const char* gather_aug_check(long long B, long long D, long long H, long long W, long long Cin, long long Cpad,
-                             long long K);
-hipError_t gather_batch_aug_launch(const float* x_all, const float* y_all, const long long* idx, const int* code,
-                                   const float* affine, int B, int D, int H, int W, int Cin, int Cpad, int K, void* xb,
-                                   void* tb, hipStream_t s);
-// gather_batch_aug reading a D x H x W patch at origin (int32 [B][3] = (d, h, w), clamped into
-// the sample by the kernel) of stored Ds x Hs x Ws samples (gather_crop.h); code may be null
-// (= 0); H == W, patch <= stored on every axis
-const char* gather_crop_check(long long B, long long Ds, long long Hs, long long Ws, long long D, long long H,
-                              long long W, long long Cin, long long Cpad, long long K);
-hipError_t gather_batch_crop_launch(const float* x_all, const float* y_all, const long long* idx, const int* origin,
-                                    const int* code, const float* affine, int B, int Ds, int Hs, int Ws, int D, int H,
-                                    int W, int Cin, int Cpad, int K, void* xb, void* tb, hipStream_t s);
-// gather_batch_crop resampled through a per-sample Q16 matrix in the (H, W) plane (mat int32
-// [B][4], entries clamped into [-2^18, 2^18] by the kernel): bilinear image, nearest target,
-// zero outside the stored image (gather_warp.h); origin may be null (= 0), code may be null (= 0)
-const char* gather_warp_check(long long B, long long Ds, long long Hs, long long Ws, long long D, long long H,
-                              long long W, long long Cin, long long Cpad, long long K);
-hipError_t gather_batch_warp_launch(const float* x_all, const float* y_all, const long long* idx, const int* origin,
-                                    const int* code, const int* mat, const float* affine, int B, int Ds, int Hs,
-                                    int Ws, int D, int H, int W, int Cin, int Cpad, int K, void* xb, void* tb,
-                                    hipStream_t s);
-// gather_batch_warp with a per-pixel displacement added to the source coordinates: a quadratic
-// B-spline through field int32 [B][N][N][2] (2^-17 pixel, entries clamped into [-2^22, 2^22] by the
-// kernel), N = ((H - 1) >> s) + 3, cells of 1 << s patch pixels (gather_elastic.h); mat may be null
-// (= the identity), origin and code as in the warp
-const char* gather_elastic_check(long long B, long long Ds, long long Hs, long long Ws, long long D, long long H,
-                                 long long W, long long Cin, long long Cpad, long long K, long long s);
-hipError_t gather_batch_elastic_launch(const float* x_all, const float* y_all, const long long* idx,
-                                       const int* origin, const int* code, const int* mat, const float* affine,
-                                       const int* field, int B, int Ds, int Hs, int Ws, int D, int H, int W, int Cin,
-                                       int Cpad, int K, int s, void* xb, void* tb, hipStream_t st);
+// the four batch gathers with a per-sample transform riding on the pass (gather.h,
+// gather_resample.h; GatherOp and GatherArgs: conv_params.h).  aug: a code (int32 [B]: bit 0 flip
+// W, 1 flip H, 2 swap H and W, 3 flip D) and an optional per-channel affine (fp32 [B][Cin][2] =
+// {scale, shift}) on the image; crop: the same on a D x H x W patch at origin (int32 [B][3] = (d,
+// h, w), clamped into the sample by the kernel) of stored Ds x Hs x Ws samples; warp: the patch
+// resampled through a Q16 matrix in the (H, W) plane (mat int32 [B][4], entries clamped into
+// [-2^18, 2^18]): bilinear image, nearest target, zero outside the stored image; elastic: the
+// warp with a per-pixel displacement of the source coordinates, a quadratic B-spline through
+// field int32 [B][N][N][2] (2^-17 pixel, entries clamped into [-2^22, 2^22]), N = ((H - 1) >> s)
+// + 3, cells of 1 << s patch pixels.  H == W, patch <= stored on every axis.  Required besides
+// x_all, y_all, idx, xb and tb: code (aug), origin (crop), mat (warp), field (elastic); every
+// other pointer may be null (origin, code = 0; mat = the identity)
+const char* gather_check(GatherOp op, const GatherArgs& a);
+hipError_t gather_launch(GatherOp op, const GatherArgs& a, void* xb, void* tb, hipStream_t s);
 // code: optional uint32 per (pooled pixel, 8 channels) = first-argmax index per channel
 // (2 / 3 bits); the backward reads it instead of x when non-null
 hipError_t maxpool2_fwd_launch(const void* x, int N, int D, int H, int W, int C, int dims3, void* y, void* code,
@@ -236,25 +215,8 @@ hipError_t f32_colsum_launch(const float* x, long long rows, int C, int blocks, 
 // seg_stats with an fp32 target (f32_seg_stats.hip)
 hipError_t f32_seg_stats_launch(const float* prob, const float* t, int N, int S, int K, float thr, float* partial,
                                 float* stats, hipStream_t s);
-// gather_batch_aug with fp32 outputs (f32_gather_aug.hip)
-hipError_t f32_gather_batch_aug_launch(const float* x_all, const float* y_all, const long long* idx, const int* code,
-                                       const float* affine, int B, int D, int H, int W, int Cin, int Cpad, int K,
-                                       float* xb, float* tb, hipStream_t s);
-// gather_batch_crop with fp32 outputs (f32_gather_crop.hip)
-hipError_t f32_gather_batch_crop_launch(const float* x_all, const float* y_all, const long long* idx,
-                                        const int* origin, const int* code, const float* affine, int B, int Ds, int Hs,
-                                        int Ws, int D, int H, int W, int Cin, int Cpad, int K, float* xb, float* tb,
-                                        hipStream_t s);
-// gather_batch_warp with fp32 outputs (f32_gather_warp.hip)
-hipError_t f32_gather_batch_warp_launch(const float* x_all, const float* y_all, const long long* idx,
-                                        const int* origin, const int* code, const int* mat, const float* affine, int B,
-                                        int Ds, int Hs, int Ws, int D, int H, int W, int Cin, int Cpad, int K,
-                                        float* xb, float* tb, hipStream_t s);
-// gather_batch_elastic with fp32 outputs (f32_gather_elastic.hip)
-hipError_t f32_gather_batch_elastic_launch(const float* x_all, const float* y_all, const long long* idx,
-                                           const int* origin, const int* code, const int* mat, const float* affine,
-                                           const int* field, int B, int Ds, int Hs, int Ws, int D, int H, int W,
-                                           int Cin, int Cpad, int K, int s, float* xb, float* tb, hipStream_t st);
+// gather_launch with fp32 outputs (f32_gather.hip)
+hipError_t f32_gather_launch(GatherOp op, const GatherArgs& a, void* xb, void* tb, hipStream_t s);
 // surf_dist with an fp32 target (f32_surf_dist.hip)
 hipError_t f32_surf_dist_launch(const float* prob, const float* t, int N, int D, int H, int W, int K, float thr,
                                 int* field, int* surf, hipStream_t s);

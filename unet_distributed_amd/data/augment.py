@@ -14,20 +14,20 @@ sample's parameters do not depend on the rank, the world size or its place in th
 batch, so data-parallel runs of any width see one augmented global batch and a resumed
 run repeats the run it resumes.  :func:`apply_torch` is the transform in plain torch
 (the ATen backend, streamed data, and the oracle of the HIP kernel
-``csrc/kernels/gather_aug.h``, which applies the same parameters inside the resident
+``csrc/kernels/gather.h``, which applies the same parameters inside the resident
 batch gather).
 
 ``--crop`` adds a patch origin per sample: :func:`draw_crop` draws it from hash words of its
 own (the codes and affines above do not change), :func:`crop_torch` is the crop in plain
 torch, and the whole transform is ``apply_torch(*crop_torch(x, y, origin, patch), code,
-affine)`` -- the oracle of ``csrc/kernels/gather_crop.h``.
+affine)`` -- the oracle of ``csrc/kernels/gather.h``.
 
 ``--augment rotate,scale`` adds a 2 x 2 matrix per sample in Q16, rotation by any angle and
 isotropic zoom in the (H, W) plane: :func:`draw_spatial` draws it from hash words of its own,
 :func:`warp_torch` resamples the patch through it straight from the stored sample (bilinear
 image, nearest target, zero outside the image) in integer coordinates, and the whole transform
 is ``apply_torch(*warp_torch(x, y, origin, patch, mat), code, affine)`` -- the oracle of
-``csrc/kernels/gather_warp.h``.
+``csrc/kernels/gather_resample.h``.
 
 ``--augment elastic`` adds a smooth random deformation: :func:`draw_elastic` draws a lattice of
 control-node displacements per sample (``--augment_elastic`` pixels of standard deviation, cells
@@ -36,7 +36,7 @@ evaluates the integer quadratic B-spline through them at every patch pixel, and
 :func:`elastic_torch` is warp_torch with that displacement added to its source coordinates (the
 matrix is the identity without rotate / scale).  The whole transform is
 ``apply_torch(*elastic_torch(x, y, origin, patch, mat, field, S), code, affine)`` -- the oracle
-of ``csrc/kernels/gather_elastic.h``.  The order stays crop, resample, flip / quarter turns,
+of ``csrc/kernels/gather_resample.h``.  The order stays crop, resample, flip / quarter turns,
 jitter.
 """
 
@@ -243,7 +243,7 @@ def warp_torch(x, y, origin, patch, mat):
     (Qw + 65536) >> 17).  The whole training transform is
     ``apply_torch(*warp_torch(x, y, origin, patch, mat), code, affine)`` straight from the stored
     samples -- taps outside the patch rectangle read the stored image -- and the oracle of
-    ``csrc/kernels/gather_warp.h``."""
+    ``csrc/kernels/gather_resample.h``."""
     return _resample("warp_torch", x, y, origin, patch, mat, None)
 
 
@@ -401,7 +401,7 @@ def elastic_torch(x, y, origin, patch, mat, field, S: int):
     target, zero outside the stored image; every depth slice of a sample uses the same field.
     The whole training transform is ``apply_torch(*elastic_torch(...), code, affine)`` -- the
     displacement is indexed by the patch pixel before the flip / transpose code -- and the oracle
-    of ``csrc/kernels/gather_elastic.h``."""
+    of ``csrc/kernels/gather_resample.h``."""
     import torch
     fl = field.cpu() if isinstance(field, torch.Tensor) else field
     if len(fl) != x.shape[0]:

@@ -16,7 +16,7 @@ from typing import Optional, Tuple
 import torch
 
 from .. import native
-from .plan_check import RecordingPlan
+from .plan_check import GATHER_OPS, RecordingPlan
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -276,14 +276,14 @@ class ExecutorBase:
         and cast straight into the (padded) input and the target (one launch).  `aug`:
         optional (code int32 [B], affine float32 [B][Cin][2] or None) on the device
         (data/augment.py): the same launch flips / rotates each sample and applies its
-        per-channel affine (kernels/gather_aug.h).  `crop`: optional (origin int32 [B][3] on
+        per-channel affine (kernels/gather.h).  `crop`: optional (origin int32 [B][3] on
         the device, patch dims): the stored samples are larger than the model's input and the
-        launch reads each sample's patch at its origin, then transforms it (kernels/gather_crop.h).
+        launch reads each sample's patch at its origin, then transforms it (the same kernels).
         An `aug` of three items (code or None, affine or None, mat int32 [B][4]) resamples the
         patch -- the whole sample without `crop` -- through each sample's matrix in the same
-        launch (kernels/gather_warp.h).  An `aug` of four items (code or None, affine or None, mat or
+        launch (kernels/gather_resample.h).  An `aug` of four items (code or None, affine or None, mat or
         None, field int32 [B][N][N][2]) adds the elastic displacement of each sample's field to
-        the warp's source coordinates (kernels/gather_elastic.h): `elastic_cell` is the side S of a
+        the warp's source coordinates (the same kernels): `elastic_cell` is the side S of a
         lattice cell in patch pixels and N = ((H - 1) >> log2 S) + 3."""
         if aug is None and crop is None:
             return self._load_plain(x_all, y_all, idx, stream)
@@ -340,14 +340,11 @@ class ExecutorBase:
         if affine is not None and (affine.dtype != torch.float32 or tuple(affine.shape) != (B, cin, 2)
                                    or affine.device != dev or not affine.is_contiguous()):
             raise ValueError("augmentation affine: a contiguous float32 [%d][%d][2] tensor on %s" % (B, cin, dev))
-        whole = name == "gather_batch_aug"
-        if field is not None:
-            ptrs = [x_all, y_all, idx, origin, code, mat, affine, field, self.bufs["x"], self.target]
-        else:
-            ptrs = ([x_all, y_all, idx] + ([] if whole else [origin]) + [code] + ([] if mat is None else [mat])
-                    + [affine, self.bufs["x"], self.target])
-        ints = [B] + list(stored) + ([] if whole else list(patch)) + [cin, self.cpad, self.K] + (
-            [] if field is None else [slog])
+        row = GATHER_OPS[name]
+        own = {"origin": origin, "code": code, "mat": mat, "affine": affine, "field": field}
+        ptrs = [x_all, y_all, idx] + [own[k] for k in row.slots] + [self.bufs["x"], self.target]
+        ints = [B] + (list(stored) if row.patch == 4 else []) + list(patch) + [cin, self.cpad, self.K] + (
+            [slog] if "field" in row.slots else [])
         return name, [0 if t is None else _ptr(t) for t in ptrs], ints
 
     # ------------------------------------------------------------------ evaluation

@@ -21,7 +21,7 @@ The reference has no such machinery (its graph is TF's, `test_dist.py:183-298`);
 the static-graph executor's equivalent of TF's graph validation.
 """
 
-from typing import Dict, List, Tuple
+from typing import Dict, List, NamedTuple, Tuple
 
 import torch
 
@@ -32,6 +32,31 @@ CONV_WRITES = ("dst1", "dst2", "stats", "relu_bits", "pool_dst", "head_logit", "
                "fw_bias_slab")
 WGRAD_READS = ("a1", "a2", "b", "xa", "xb", "xc", "xz") + _HG
 WGRAD_WRITES = ("slab", "bias_slab")
+
+
+class GatherRow(NamedTuple):
+    """Layout of one batch gather's generic op (bindings.cpp): ptrs = x_all, y_all, idx, `slots`,
+    xb, tb; ints = B, (Ds, Hs, Ws when `patch` is 4,) D, H, W, Cin, Cpad, K (, s for the elastic op)."""
+    slots: Tuple[str, ...]      # the op's own pointers, in order
+    nints: int
+    patch: int                  # index of the patch's D in ints
+
+    @property
+    def xb(self) -> int:        # index of xb in ptrs; tb follows it
+        return 3 + len(self.slots)
+
+
+GATHER_OPS = {
+    "gather_batch_aug": GatherRow(("code", "affine"), 7, 1),
+    "gather_batch_crop": GatherRow(("origin", "code", "affine"), 10, 4),
+    "gather_batch_warp": GatherRow(("origin", "code", "mat", "affine"), 10, 4),
+    "gather_batch_elastic": GatherRow(("origin", "code", "mat", "affine", "field"), 11, 4),
+}
+
+
+def _gather_row(kind: str):
+    """The row of generic op `kind` (16-bit or "f32_") in GATHER_OPS, or None."""
+    return GATHER_OPS.get(kind[4:] if kind.startswith("f32_") else kind)
 
 
 def _sel(p, idx):
@@ -115,29 +140,12 @@ def _generic_write_spans(kind: str, p: List[int], ints: List[int]) -> List[Tuple
     # label map (N, D, H, W, K, Do, Ho, Wo in ints): the whole uint8 destination and N 5 ints of counts
     if kind == "labelmap" and len(p) > 2 and len(ints) >= 8:
         return [(p[1], ints[0] * ints[5] * ints[6] * ints[7]), (p[2], ints[0] * 5 * 4)]
-    # augmenting batch gather (B, D, H, W, Cin, Cpad, K in ints): the padded input and the target,
-    # 16-bit (gather_batch_aug) or fp32 (f32_gather_batch_aug)
-    if kind in ("gather_batch_aug", "f32_gather_batch_aug") and len(p) > 6 and len(ints) >= 7:
-        B, D, H, W, _, cpad, K = ints[:7]
+    # the batch gathers: the padded input and the target of the patch's size, 16-bit or fp32 (f32_)
+    g = _gather_row(kind)
+    if g and len(p) > g.xb + 1 and len(ints) >= g.nints:
+        B, (D, H, W, _, cpad, K) = ints[0], ints[g.patch:g.patch + 6]
         eb = 4 if kind.startswith("f32") else 2
-        return [(p[5], B * D * H * W * cpad * eb), (p[6], B * D * H * W * K * eb)]
-    # cropping batch gather (B, Ds, Hs, Ws, D, H, W, Cin, Cpad, K in ints): the same two buffers,
-    # of the patch's size
-    if kind in ("gather_batch_crop", "f32_gather_batch_crop") and len(p) > 7 and len(ints) >= 10:
-        B, _, _, _, D, H, W, _, cpad, K = ints[:10]
-        eb = 4 if kind.startswith("f32") else 2
-        return [(p[6], B * D * H * W * cpad * eb), (p[7], B * D * H * W * K * eb)]
-    # resampling batch gather (the same ints; one more pointer, the matrices, before the affine)
-    if kind in ("gather_batch_warp", "f32_gather_batch_warp") and len(p) > 8 and len(ints) >= 10:
-        B, _, _, _, D, H, W, _, cpad, K = ints[:10]
-        eb = 4 if kind.startswith("f32") else 2
-        return [(p[7], B * D * H * W * cpad * eb), (p[8], B * D * H * W * K * eb)]
-    # elastic batch gather (the warp's ints and the cell's log2; one more pointer, the field, after
-    # the affine)
-    if kind in ("gather_batch_elastic", "f32_gather_batch_elastic") and len(p) > 9 and len(ints) >= 11:
-        B, _, _, _, D, H, W, _, cpad, K = ints[:10]
-        eb = 4 if kind.startswith("f32") else 2
-        return [(p[8], B * D * H * W * cpad * eb), (p[9], B * D * H * W * K * eb)]
+        return [(p[g.xb], B * D * H * W * cpad * eb), (p[g.xb + 1], B * D * H * W * K * eb)]
     # test-time augmentation: the fp32 accumulator (N, D, H, W, K in ints); the finish (total
     # elements in ints) rewrites prob and writes one row of 4 floats per block and the 4 sums
     if kind == "tta_acc" and len(p) > 1 and len(ints) >= 5:
@@ -245,14 +253,9 @@ def _generic_rw(kind: str, p: List[int], ints: List[int]) -> Tuple[List[int], Li
         return _sel(p, [0]), _sel(p, [1, 2, 3])
     if kind == "labelmap":
         return _sel(p, [0]), _sel(p, [1, 2])
-    if kind in ("gather_batch_aug", "f32_gather_batch_aug"):
-        return [q for q in _sel(p, [0, 1, 2, 3, 4]) if q], _sel(p, [5, 6])
-    if kind in ("gather_batch_crop", "f32_gather_batch_crop"):
-        return [q for q in _sel(p, [0, 1, 2, 3, 4, 5]) if q], _sel(p, [6, 7])
-    if kind in ("gather_batch_warp", "f32_gather_batch_warp"):
-        return [q for q in _sel(p, [0, 1, 2, 3, 4, 5, 6]) if q], _sel(p, [7, 8])
-    if kind in ("gather_batch_elastic", "f32_gather_batch_elastic"):
-        return [q for q in _sel(p, [0, 1, 2, 3, 4, 5, 6, 7]) if q], _sel(p, [8, 9])
+    g = _gather_row(kind)
+    if g:                                # (a null origin, code, matrix or affine is not read)
+        return [q for q in p[:g.xb] if q], _sel(p, [g.xb, g.xb + 1])
     if kind == "tta_acc":                # (write mode reads no element of the accumulator)
         return _sel(p, [0, 1] if len(ints) > 6 and ints[6] else [0]), _sel(p, [1])
     if kind in ("tta_finish", "f32_tta_finish"):
