@@ -104,10 +104,11 @@ class Config:
     loss_scale: float = 0.0          # fp16 static loss scale (0 = dynamic)
     eval_threshold: float = 0.5      # probability threshold of the per-case (hard) evaluation metrics
     eval_hd95: bool = False          # evaluation also reports the per-case 95th-percentile Hausdorff distance
-    augment: str = ""                # training batches only: comma-separated subset of flip, rot90, intensity, rotate, scale, elastic
+    augment: str = ""                # training batches only: comma-separated subset of flip, rot90, intensity, rotate, scale, elastic, rotate3d, scale3d
     augment_intensity: float = 0.1   # intensity: scale in [1-a, 1+a], shift in [-a, a] per (sample, channel)
     augment_rotate: float = 30.0     # rotate: angle uniform in [-r, r] degrees per sample, r in (0, 180]
     augment_scale: float = 0.25      # scale: zoom log-uniform in [1/(1+a), 1+a] per sample, a in (0, 1]
+    augment_rotate3d: float = 15.0   # rotate3d: the two out-of-plane angles uniform in [-r, r] degrees, r in (0, 180]
     augment_elastic: float = 4.0     # elastic: standard deviation of a control node's displacement, stored-image pixels
     augment_elastic_cell: int = 32   # elastic: side of a control-lattice cell in patch pixels, 8, 16, 32 or 64
     eval_tta: str = ""               # evaluation only: mean prediction over flip and / or rot90 (comma-separated)
@@ -140,8 +141,9 @@ _CHOICES = {
 }
 
 
-AUGMENT_NAMES = ("flip", "rot90", "intensity", "rotate", "scale", "elastic")
+AUGMENT_NAMES = ("flip", "rot90", "intensity", "rotate", "scale", "elastic", "rotate3d", "scale3d")
 SPATIAL_NAMES = ("rotate", "scale")  # the transforms that resample the image (data/augment.py draw_spatial)
+SPATIAL3_NAMES = ("rotate3d", "scale3d")  # ... through a 3 x 3 matrix over (d, h, w), --dims 3 (draw_spatial3)
 ELASTIC_CELLS = (8, 16, 32, 64)      # --augment_elastic_cell (data/augment.py draw_elastic)
 
 
@@ -293,7 +295,18 @@ def validate(cfg: Config) -> None:
     if not 0.0 < cfg.augment_scale <= 1.0:
         raise SystemExit("--augment_scale must be in (0, 1]: the zoom is drawn from [1/(1+a), 1+a], got %r"
                          % (cfg.augment_scale,))
-    if "elastic" in parse_augment(cfg.augment):
+    if not 0.0 < cfg.augment_rotate3d <= 180.0:
+        raise SystemExit("--augment_rotate3d must be in (0, 180]: the largest out-of-plane angle in degrees, got %r"
+                         % (cfg.augment_rotate3d,))
+    names = parse_augment(cfg.augment)
+    for t in SPATIAL3_NAMES:
+        if t in names and cfg.dims != 3:
+            raise SystemExit("--augment %s needs --dims 3 (it resamples along depth), got --dims %d" % (t, cfg.dims))
+    if "rotate" in names and "rotate3d" in names:
+        raise SystemExit("--augment: rotate together with rotate3d (rotate3d includes the in-plane rotation)")
+    if "scale" in names and "scale3d" in names:
+        raise SystemExit("--augment: scale together with scale3d (scale3d includes the in-plane zoom)")
+    if "elastic" in names:
         # node values are truncated at +-2a, so neighbouring nodes differ by at most 4a and the
         # quadratic B-spline's derivative is at most 4a / S: a <= S / 8 keeps it within 1/2
         S, a = cfg.augment_elastic_cell, cfg.augment_elastic

@@ -314,11 +314,12 @@ struct SwGeo {
   int B, t0, nt;
 };
 
-// The four batch gathers of gather.h / gather_resample.h and the arguments of one launch: a
+// The five batch gathers of gather.h / gather_resample.h and the arguments of one launch: a
 // D x H x W patch of stored Ds x Hs x Ws samples.  aug has no stored size and no origin (the
 // launcher sets stored = patch); a pointer an op does not take is null; s: log2 of the elastic
 // cell side.  The integers are 64-bit so that gather_check sees what the caller passed.
-enum class GatherOp { aug, crop, warp, elastic };
+// warp3: mat is [B][9], and field may be null (no displacement; s is then not read).
+enum class GatherOp { aug, crop, warp, elastic, warp3 };
 struct GatherArgs {
   const float *x_all, *y_all;
   const long long* idx;
@@ -329,7 +330,7 @@ struct GatherArgs {
 };
 // the op's own required pointer, besides x_all, y_all, idx and the two outputs
 inline const int* gather_required(GatherOp op, const GatherArgs& a) {
-  return op == GatherOp::aug ? a.code : op == GatherOp::crop ? a.origin : op == GatherOp::warp ? a.mat : a.field;
+  return op == GatherOp::aug ? a.code : op == GatherOp::crop ? a.origin : op == GatherOp::elastic ? a.field : a.mat;
 }
 
 }  // namespace unet_types

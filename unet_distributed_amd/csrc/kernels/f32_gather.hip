@@ -1,4 +1,4 @@
-// The four batch gathers with fp32 outputs (the fp32 executor's input and target buffers,
+// The five batch gathers with fp32 outputs (the fp32 executor's input and target buffers,
 // Cpad = Cin): element-type independent, built once (gather.h, gather_resample.h; the shape
 // check: gather.hip).
 #include "gather_resample.h"

@@ -3,7 +3,7 @@
 // top of it, a smooth per-pixel displacement of the source coordinates, a quadratic B-spline
 // through a per-sample lattice of control-node displacements: gather_batch_elastic.  One pass;
 // the image is interpolated bilinearly, the target is read at the nearest voxel.  The launcher
-// of all four gathers, gather_launch_t, is at the end of this file.
+// of all five gathers, gather_launch_t, is at the end of this file.
 //
 //   x_all, y_all, idx, origin, code, affine, xb, tb: as in gather.h
 //   mat    int32 [B][4] = (a00, a01, a10, a11), Q16; elastic: or null (= the identity)
@@ -55,20 +55,58 @@
 //
 // Any other Cpad <= 64: one lane per output pixel, the nine nodes read from global memory.
 // Plain vector loads and stores only: no atomics, two runs give the same bits.
+//
+// gather_batch_warp3 (WARP3 on the same two kernels): the matrix is 3 x 3 over (d, h, w), mat int32
+// [B][9] row-major and required, and depth is rotated, zoomed and interpolated too (data/augment.py
+// warp3_torch, bit for bit).  At patch coordinates (d', h', w'), d' = FD ? D-1-d : d:
+//   t = 2 d' - (D - 1)
+//   Qd = (origin.d << 17) + (D - 1) 65536 + m00 t + m01 u + m02 v,  Qh, Qw alike from rows 1 and 2
+// D < 2^16 (gather_check), so |t| < 2^16 and |Q| < 2^38 as above.  id = Qd >> 17, fd = Qd & 0x1FFFF;
+// s0 and s1 are the bilinear value above in the slices id and id + 1 (a tap whose slice is
+// outside the stored volume is 0.0f too, its address clamped) and the voxel is
+//   s0 wd0 + s1 wd1,  wd1 = fd 2^-17,  wd0 = (131072 - fd) 2^-17
+// two products and one sum, each rounded once.  Target: y at ((Qd + 65536) >> 17, nh, nw), 0.0f
+// outside.  field may be null (no displacement: the ELASTIC = false instantiation); with one the
+// displacement above is added to Qh and Qw, the same in every slice.  A lane issues 8 taps and 1
+// target voxel per output voxel, all before the first use.
+// Tiled kernel: a wave is 8 x 4 voxels in each of 2 adjacent output slices and a lane owns 2 voxels
+// at Cpad 4 (104 VGPRs, 4 waves / SIMD) and 1 at Cpad 8 (92 VGPRs, 5 waves), no scratch; a
+// workgroup is 32 x 4 x 2 voxels per pass.  Once the plane tilts, a 16 x 4 tile in one slice walks
+// across 16 sin(theta) source slices, each a line Hs Ws Cin 4 bytes away.  Measured at b8, 128^3 x 4
+// of 155 x 240 x 240 x 4, bf16, us per launch for the identity / drawn matrices at the defaults / 30
+// degrees about d, h, w / drawn with mixed codes (profiles/r21_rotate3d.md):
+//   16 x 4 x 1, 2 passes:  173 / 268 / 205, 391, 181 / 308        (102 VGPRs)
+//    8 x 4 x 2, 2 passes:  174 / 252 / 225, 276, 178 / 290        (kept)
+//    4 x 4 x 4, 2 passes:  204 / 287 / 274, 276, 203 / 304        (104 VGPRs)
+//   16 x 4 x 1, 4 passes:  244 / 281 / 258, 344, 244 / 306        (202 VGPRs, 2 waves / SIMD)
+//   16 x 4 x 1, 1 pass:    160 / 285 / 226, 380, 164 / 310        (54 VGPRs, 8 waves / SIMD)
+//    4 x 4 x 4, 1 pass:    239 / 298 / 283, 278, 231 / 319
+// against 152 us of the in-plane warp with drawn matrices and mixed codes.  The Cpad 8 pass count
+// with 2 passes (168 VGPRs, 3 waves) was compiled but not timed; 8 x 4 x 2 with 1 pass was not tried.
 #pragma once
 #include "gather.h"
 
 namespace unet {
 namespace {
 
-constexpr int GW_TW_LOG2 = 4;                     // wave tile: 16 pixels along W ...
-constexpr int GW_TW = 1 << GW_TW_LOG2;
-constexpr int GW_TH = 64 / GW_TW;                 // ... by 4 along H
-constexpr int GW_WGW = GW_TW < 32 ? 32 : GW_TW;   // workgroup: waves side by side up to 32 pixels,
-constexpr int GW_ACROSS = GW_WGW / GW_TW;
-constexpr int GW_PH = GW_TH * (GA_THREADS / 64 / GW_ACROSS);    // the rest stacked: rows per pass
-constexpr int GW_PX = 4;                          // passes = pixels per lane
-constexpr int GW_TILE_H = GW_PH * GW_PX;
+// the wave tile of 64 output voxels: 16 x 4 in one slice (TDL = 0), 8 x 4 in each of 2 slices
+// (TDL = 1) or 4 x 4 in each of 4 (TDL = 2); always 4 along H.  A workgroup of 4 waves puts them
+// side by side up to 32 voxels along W and stacks the rest along H: PH rows per pass
+template <int TDL>
+struct GwGeo {
+  static constexpr int TW_LOG2 = 4 - TDL, TW = 1 << TW_LOG2, TH = 4, TD = 1 << TDL;
+  static constexpr int ACROSS = 32 / TW < GA_THREADS / 64 ? 32 / TW : GA_THREADS / 64;
+  static constexpr int WGW = ACROSS * TW;
+  static constexpr int PH = TH * (GA_THREADS / 64 / ACROSS);
+};
+constexpr int GW_PX = 4;                          // passes = pixels per lane (warp, elastic)
+// ... of the 3D warp (8 taps per voxel: 2 passes at Cpad 4, 1 at Cpad 8) and its wave tile, 8 x 4 in
+// each of 2 slices (GwGeo)
+constexpr int GW3_TDL = 1;
+template <int CPAD>
+struct Gw3Px {
+  static constexpr int value = CPAD == 4 ? 2 : 1;
+};
 constexpr int GW_MAT_MAX = 1 << 18;               // clamp of a matrix entry (Q16: a zoom of 1/4)
 constexpr int GE_FIELD_MAX = 1 << 22;             // clamp of a field entry (2^-17 pixel: 32 pixels)
 constexpr int GE_NODES = 7;                       // nodes per axis a 32-pixel span can touch at S = 8
@@ -145,6 +183,52 @@ __device__ __forceinline__ float gw_lerp(float p00, float p01, float p10, float 
   return e + f;
 }
 
+// warp3: the sample's clamped 3 x 3 matrix over (d, h, w) and the patch centre in 2^-17 voxel of
+// the stored volume; gw3_source gives the source coordinates of patch voxel (pd, ph, pw)
+struct Gw3Map {
+  long long cd, ch, cw;
+  int m[9];
+};
+__device__ __forceinline__ Gw3Map gw3_map(const int* __restrict__ mat, int n, const GcOrigin& og, int D, int H,
+                                          int W) {
+  Gw3Map g;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) g.m[e] = min(max(mat[9 * (size_t)n + e], -GW_MAT_MAX), GW_MAT_MAX);
+  g.cd = ((long long)og.d << 17) + (long long)(D - 1) * 65536;
+  g.ch = ((long long)og.h << 17) + (long long)(H - 1) * 65536;
+  g.cw = ((long long)og.w << 17) + (long long)(W - 1) * 65536;
+  return g;
+}
+__device__ __forceinline__ void gw3_source(const Gw3Map& g, int pd, int ph, int pw, int D, int H, int W,
+                                           long long& qd, long long& qh, long long& qw) {
+  const long long t = 2 * pd - (D - 1), u = 2 * ph - (H - 1), v = 2 * pw - (W - 1);
+  qd = g.cd + g.m[0] * t + g.m[1] * u + g.m[2] * v;
+  qh = g.ch + g.m[3] * t + g.m[4] * u + g.m[5] * v;
+  qw = g.cw + g.m[6] * t + g.m[7] * u + g.m[8] * v;
+}
+
+// warp3: the two clamped slices of a voxel at depth qd, their validity and weights, and the
+// nearest slice of the target
+struct GwDepth {
+  int s0, s1, ns;
+  bool s0ok, s1ok, nok;
+  float wd0, wd1;
+};
+__device__ __forceinline__ GwDepth gw_depth(long long qd, int Ds) {
+  const int id = (int)(qd >> 17), fd = (int)(qd & 0x1FFFF), nd = (int)((qd + 65536) >> 17);
+  GwDepth z;
+  z.s0ok = id >= 0 && id < Ds, z.s1ok = id + 1 >= 0 && id + 1 < Ds, z.nok = nd >= 0 && nd < Ds;
+  z.s0 = min(max(id, 0), Ds - 1), z.s1 = min(max(id + 1, 0), Ds - 1), z.ns = min(max(nd, 0), Ds - 1);
+  z.wd1 = (float)fd * 0x1p-17f, z.wd0 = (float)(131072 - fd) * 0x1p-17f;
+  return z;
+}
+// s0 wd0 + s1 wd1 of the two slices' bilinear values: two products and one sum, each rounded once
+__device__ __forceinline__ float gw_lerp_depth(float s0, float s1, const GwDepth& z) {
+#pragma clang fp contract(off)
+  const float e = s0 * z.wd0, f = s1 * z.wd1;
+  return e + f;
+}
+
 // the integer quadratic B-spline weights of offset t inside a cell of S = 1 << s pixels
 __device__ __forceinline__ void ge_weights(int t, int s, int w[3]) {
   const int S = 1 << s;
@@ -158,33 +242,49 @@ __device__ __forceinline__ int* ge_node_lds() {
   return fs;
 }
 
-// grid: B * D * th * tw workgroups of a GW_WGW x GW_TILE_H pixel tile each; field and s are read
-// with ELASTIC only
-template <int CPAD, typename TT, bool ELASTIC>
+// grid: B * ceil(D / TD) * th * tw workgroups of a WGW x (PH PX) pixel tile in each of TD slices
+// (GwGeo<TDL>; warp and elastic: one slice, 32 x 32); field and s are read with ELASTIC only.
+// WARP3: mat is [B][9] and not null, depth is interpolated, and ELASTIC says a field was given
+template <int CPAD, typename TT, bool ELASTIC, bool WARP3 = false, int PX = GW_PX, int TDL = 0>
 __global__ void __launch_bounds__(GA_THREADS) gather_resample_tile_kernel(
     const float* __restrict__ x_all, const float* __restrict__ y_all, const long long* __restrict__ idx,
     const int* __restrict__ origin, const int* __restrict__ code, const int* __restrict__ mat,
     const float* __restrict__ affine, const int* __restrict__ field, int Ds, int Hs, int Ws, int D, int H, int th,
     int tw, int Cin, int K, int s, TT* __restrict__ xb, TT* __restrict__ tb) {
 #pragma clang fp contract(off)
-  constexpr int NW = GaLayout<CPAD, TT>::NW;
+  using G = GwGeo<TDL>;
+  constexpr int NW = GaLayout<CPAD, TT>::NW, TILE_H = G::PH * PX, TAPS = WARP3 ? 8 : 4;
+  static_assert(WARP3 || TDL == 0, "only the 3D warp spreads a wave over slices");
+  static_assert(TILE_H <= 32 && G::WGW <= 32, "the staged nodes cover a span of 32 pixels per axis");
   const int W = H;
   int bid = blockIdx.x;
   const int tj = bid % tw;
   bid /= tw;
   const int ti = bid % th;
   bid /= th;
-  const int d = bid % D, n = bid / D;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nsl = (D + G::TD - 1) >> TDL;            // groups of TD output slices
+  const int n = bid / nsl;
+  const int d = ((bid % nsl) << TDL) + (lane >> (G::TW_LOG2 + 2));     // TDL = 0: the workgroup's slice
   const int cd = ga_code(code, n, D);
   const bool fw = cd & 1, fh = cd & 2, tr = cd & 4;
   const GcOrigin og = gc_origin(origin, n, Ds, Hs, Ws, D, H, W);
-  GwMap g = gw_map(mat, n, og, H, W);
-  if constexpr (!ELASTIC) gw_fold(g, cd);
-  const size_t sbase = ga_slice(idx, n, d, cd, og, Ds, Hs, Ws, D);
+  GwMap g = {};
+  Gw3Map g3 = {};
+  size_t sbase = 0;
+  if constexpr (WARP3) {
+    g3 = gw3_map(mat, n, og, D, H, W);
+    sbase = (size_t)idx[n] * Ds;                     // the sample's slice 0, in slices
+  } else {
+    g = gw_map(mat, n, og, H, W);
+    if constexpr (!ELASTIC) gw_fold(g, cd);
+    sbase = ga_slice(idx, n, d, cd, og, Ds, Hs, Ws, D);
+  }
+  // WARP3: the lane's patch slice d' (a slice past the patch maps like the last and is never stored)
+  const int dc = min(d, D - 1), pd = (cd & 8) ? D - 1 - dc : dc;
   const size_t obase = ((size_t)n * D + d) * H * W;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ow = tj * GW_WGW + (wave % GW_ACROSS) * GW_TW + (lane & (GW_TW - 1));
-  const int oh0 = ti * GW_TILE_H + (wave / GW_ACROSS) * GW_TH + (lane >> GW_TW_LOG2);
+  const int ow = tj * G::WGW + (wave % G::ACROSS) * G::TW + (lane & (G::TW - 1));
+  const int oh0 = ti * TILE_H + (wave / G::ACROSS) * G::TH + ((lane >> G::TW_LOG2) & (G::TH - 1));
 
   float sc[CPAD], sf[CPAD];
   const bool af = ga_affine<CPAD>(affine, n, Cin, sc, sf);
@@ -201,8 +301,8 @@ __global__ void __launch_bounds__(GA_THREADS) gather_resample_tile_kernel(
     fs = ge_node_lds();
     // the tile's span of patch coordinates: output rows [ti 32, ...] and columns [tj 32, ...] clipped
     // to the patch, swapped by T and mirrored by the flips; its first cell per axis
-    const int olo_h = ti * GW_TILE_H, ohi_h = min(olo_h + GW_TILE_H, H) - 1;
-    const int olo_w = tj * GW_WGW, ohi_w = min(olo_w + GW_WGW, W) - 1;
+    const int olo_h = ti * TILE_H, ohi_h = min(olo_h + TILE_H, H) - 1;
+    const int olo_w = tj * G::WGW, ohi_w = min(olo_w + G::WGW, W) - 1;
     const int alo = tr ? olo_w : olo_h, ahi = tr ? ohi_w : ohi_h;     // h' before the flip
     const int blo = tr ? olo_h : olo_w, bhi = tr ? ohi_h : ohi_w;     // w' before the flip
     ci0 = (fh ? H - 1 - ahi : alo) >> s, cj0 = (fw ? W - 1 - bhi : blo) >> s;
@@ -222,17 +322,22 @@ __global__ void __launch_bounds__(GA_THREADS) gather_resample_tile_kernel(
   // every load of the lane's pixels is issued before the first use: no branch around them (a
   // pixel past the patch edge maps like the edge pixel and is never stored; every address is
   // clamped into the slice)
-  GwTap t[GW_PX];
-  float p[GW_PX][4][CPAD], tv[GW_PX][4];
+  GwTap t[PX];
+  GwDepth z[PX];
+  float p[PX][TAPS][CPAD], tv[PX][4];
 #pragma unroll
-  for (int i = 0; i < GW_PX; ++i) {
-    const int ohc = min(oh0 + GW_PH * i, H - 1);
-    long long qh, qw;
-    if constexpr (!ELASTIC) {
+  for (int i = 0; i < PX; ++i) {
+    const int ohc = min(oh0 + G::PH * i, H - 1);
+    long long qd = 0, qh, qw;
+    const int prow = tr ? (fw ? W - 1 - ohc : ohc) : (fh ? H - 1 - ohc : ohc);
+    if constexpr (WARP3) {
+      gw3_source(g3, pd, tr ? pcol : prow, tr ? prow : pcol, D, H, W, qd, qh, qw);
+    } else if constexpr (!ELASTIC) {
       gw_source(g, ohc, owc, H, W, qh, qw);       // (the code is in the matrix)
     } else {
-      const int prow = tr ? (fw ? W - 1 - ohc : ohc) : (fh ? H - 1 - ohc : ohc);
       gw_source(g, tr ? pcol : prow, tr ? prow : pcol, H, W, qh, qw);
+    }
+    if constexpr (ELASTIC) {
       int wrow[3];
       ge_weights(prow & ((1 << s) - 1), s, wrow);
       const int* nd = fs + ((prow >> s) - (tr ? cj0 : ci0)) * srow + bcol;
@@ -249,31 +354,58 @@ __global__ void __launch_bounds__(GA_THREADS) gather_resample_tile_kernel(
       qh += dh >> (2 + 4 * s), qw += dw >> (2 + 4 * s);
     }
     t[i] = gw_tap(qh, qw, Hs, Ws);
-    const size_t sa[4] = {sbase + (size_t)t[i].r0 * Ws + t[i].c0, sbase + (size_t)t[i].r0 * Ws + t[i].c1,
-                          sbase + (size_t)t[i].r1 * Ws + t[i].c0, sbase + (size_t)t[i].r1 * Ws + t[i].c1};
+    // the offsets of the four taps and of the nearest voxel inside a slice
+    const size_t so[4] = {(size_t)t[i].r0 * Ws + t[i].c0, (size_t)t[i].r0 * Ws + t[i].c1,
+                          (size_t)t[i].r1 * Ws + t[i].c0, (size_t)t[i].r1 * Ws + t[i].c1};
+    size_t sn = (size_t)t[i].nr * Ws + t[i].nc;
+    if constexpr (WARP3) {
+      z[i] = gw_depth(qd, Ds);
+      const size_t b0 = (sbase + z[i].s0) * Hs * Ws, b1 = (sbase + z[i].s1) * Hs * Ws;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) ga_load<CPAD>(x_all + sa[j] * Cin, Cin, p[i][j]);
-    const size_t sn = sbase + (size_t)t[i].nr * Ws + t[i].nc;
+      for (int j = 0; j < 4; ++j) {
+        ga_load<CPAD>(x_all + (b0 + so[j]) * Cin, Cin, p[i][j]);
+        ga_load<CPAD>(x_all + (b1 + so[j]) * Cin, Cin, p[i][TAPS - 4 + j]);
+      }
+      sn += (sbase + z[i].ns) * Hs * Ws;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ga_load<CPAD>(x_all + (sbase + so[j]) * Cin, Cin, p[i][j]);
+      sn += sbase;
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) tv[i][k] = k < K ? y_all[sn * K + k] : 0.f;
   }
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-  for (int i = 0; i < GW_PX; ++i) {
+  for (int i = 0; i < PX; ++i) {
     float v[CPAD];
+    bool nok = t[i].nok;
+    if constexpr (WARP3) {
+      // a tap of a slice outside the stored volume counts as 0.0f, like one of a row or column outside
 #pragma unroll
-    for (int ch = 0; ch < CPAD; ++ch) v[ch] = gw_lerp(p[i][0][ch], p[i][1][ch], p[i][2][ch], p[i][3][ch], t[i]);
+      for (int ch = 0; ch < CPAD; ++ch) {
+        float q[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) q[j] = (j < 4 ? z[i].s0ok : z[i].s1ok) ? p[i][j % TAPS][ch] : 0.f;
+        v[ch] = gw_lerp_depth(gw_lerp(q[0], q[1], q[2], q[3], t[i]), gw_lerp(q[4], q[5], q[6], q[7], t[i]), z[i]);
+      }
+      nok = nok && z[i].nok;
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < CPAD; ++ch) v[ch] = gw_lerp(p[i][0][ch], p[i][1][ch], p[i][2][ch], p[i][3][ch], t[i]);
+    }
     uint32_t w[NW];
     ga_convert<CPAD, TT>(v, af, sc, sf, Cin, w);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) tv[i][k] = t[i].nok ? tv[i][k] : 0.f;
-    const int oh = oh0 + GW_PH * i;
-    if (oh < H && ow < W) ga_store<CPAD>(xb, tb, obase + (size_t)oh * W + ow, w, tv[i], K);
+    for (int k = 0; k < 4; ++k) tv[i][k] = nok ? tv[i][k] : 0.f;
+    const int oh = oh0 + G::PH * i;
+    if (oh < H && ow < W && (!WARP3 || d < D))
+      ga_store<CPAD>(xb, tb, obase + (size_t)oh * W + ow, w, tv[i], K);
   }
 }
 
 // any Cpad <= 64: one lane per output pixel, B D H W < 2^31
-template <typename TT, bool ELASTIC>
+template <typename TT, bool ELASTIC, bool WARP3 = false>
 __global__ void __launch_bounds__(GA_THREADS) gather_resample_pixel_kernel(
     const float* __restrict__ x_all, const float* __restrict__ y_all, const long long* __restrict__ idx,
     const int* __restrict__ origin, const int* __restrict__ code, const int* __restrict__ mat,
@@ -285,9 +417,14 @@ __global__ void __launch_bounds__(GA_THREADS) gather_resample_pixel_kernel(
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const GaPixel px = ga_pixel(i, code, D, H, W);
     const GcOrigin og = gc_origin(origin, px.n, Ds, Hs, Ws, D, H, W);
-    const GwMap g = gw_map(mat, px.n, og, H, W);
-    long long qh, qw;
-    gw_source(g, px.h, px.w, H, W, qh, qw);
+    long long qd = 0, qh, qw;
+    if constexpr (WARP3) {
+      const Gw3Map g3 = gw3_map(mat, px.n, og, D, H, W);
+      gw3_source(g3, (px.cd & 8) ? D - 1 - px.d : px.d, px.h, px.w, D, H, W, qd, qh, qw);
+    } else {
+      const GwMap g = gw_map(mat, px.n, og, H, W);
+      gw_source(g, px.h, px.w, H, W, qh, qw);
+    }
     if constexpr (ELASTIC) {
       const int N = ((H - 1) >> s) + 3, cmask = (1 << s) - 1;
       int wh[3], ww[3];
@@ -304,6 +441,32 @@ __global__ void __launch_bounds__(GA_THREADS) gather_resample_pixel_kernel(
       qh += dh >> (2 + 4 * s), qw += dw >> (2 + 4 * s);
     }
     const GwTap t = gw_tap(qh, qw, Hs, Ws);
+    if constexpr (WARP3) {
+      const GwDepth z = gw_depth(qd, Ds);
+      const size_t v0 = (size_t)idx[px.n] * Ds;
+      const size_t so[4] = {(size_t)t.r0 * Ws + t.c0, (size_t)t.r0 * Ws + t.c1, (size_t)t.r1 * Ws + t.c0,
+                            (size_t)t.r1 * Ws + t.c1};
+      const float* a = x_all + (v0 + z.s0) * Hs * Ws * Cin;
+      const float* b = x_all + (v0 + z.s1) * Hs * Ws * Cin;
+      const float* af = affine ? affine + (size_t)px.n * Cin * 2 : nullptr;
+      TT* dst = xb + (size_t)i * Cpad;
+      for (int ch = 0; ch < Cpad; ++ch) {
+        float v = 0.f;
+        if (ch < Cin) {
+          float q[8];
+          for (int j = 0; j < 4; ++j) {
+            const float qa = a[so[j] * Cin + ch], qb = b[so[j] * Cin + ch];
+            q[j] = z.s0ok ? qa : 0.f, q[4 + j] = z.s1ok ? qb : 0.f;
+          }
+          v = ga_affine1(af, ch, gw_lerp_depth(gw_lerp(q[0], q[1], q[2], q[3], t),
+                                               gw_lerp(q[4], q[5], q[6], q[7], t), z));
+        }
+        dst[ch] = (TT)v;
+      }
+      const size_t sn = ((v0 + z.ns) * Hs + t.nr) * Ws + t.nc;
+      for (int k = 0; k < K; ++k) tb[(size_t)i * K + k] = (TT)(t.nok && z.nok ? y_all[sn * K + k] : 0.f);
+      continue;
+    }
     const size_t sbase = ga_slice(idx, px.n, px.d, px.cd, og, Ds, Hs, Ws, D);
     const float* s00 = x_all + (sbase + (size_t)t.r0 * Ws + t.c0) * Cin;
     const float* s01 = x_all + (sbase + (size_t)t.r0 * Ws + t.c1) * Cin;
@@ -323,7 +486,7 @@ __global__ void __launch_bounds__(GA_THREADS) gather_resample_pixel_kernel(
 // null when op accepts the shape of a (gather.hip), else the reason
 const char* gather_check(GatherOp op, const GatherArgs& a);
 
-// the launcher of the four gathers; aug: stored = patch, no origin
+// the launcher of the five gathers; aug: stored = patch, no origin
 template <typename TT>
 hipError_t gather_launch_t(GatherOp op, GatherArgs a, TT* xb, TT* tb, hipStream_t st) {
   if (gather_check(op, a) || !a.x_all || !a.y_all || !a.idx || !gather_required(op, a) || !xb || !tb)
@@ -357,7 +520,30 @@ hipError_t gather_launch_t(GatherOp op, GatherArgs a, TT* xb, TT* tb, hipStream_
     }
     return launch_status();
   }
+  if (op == GatherOp::warp3) {
+    // a null field: no displacement (the ELASTIC flag of the kernels)
+    const bool el = a.field != nullptr;
+    if (!tiled) {
+      UNET_LAUNCH((el ? gather_resample_pixel_kernel<TT, true, true> : gather_resample_pixel_kernel<TT, false, true>),
+                  dim3(blocks), dim3(GA_THREADS), 0, st, a.x_all, a.y_all, a.idx, a.origin, a.code, a.mat, a.affine,
+                  a.field, B, Ds, Hs, Ws, D, H, Cin, Cpad, K, s, xb, tb);
+      return launch_status();
+    }
+    using G = GwGeo<GW3_TDL>;
+    const int px = Cpad == 4 ? Gw3Px<4>::value : Gw3Px<8>::value;
+    const int th = (H + G::PH * px - 1) / (G::PH * px), tw = (W + G::WGW - 1) / G::WGW;
+    const long long grid = (long long)B * ((D + G::TD - 1) / G::TD) * th * tw;
+    if (grid >= (1LL << 31)) return hipErrorInvalidValue;
+    UNET_LAUNCH((Cpad == 4 ? (el ? gather_resample_tile_kernel<4, TT, true, true, Gw3Px<4>::value, GW3_TDL>
+                                 : gather_resample_tile_kernel<4, TT, false, true, Gw3Px<4>::value, GW3_TDL>)
+                           : (el ? gather_resample_tile_kernel<8, TT, true, true, Gw3Px<8>::value, GW3_TDL>
+                                 : gather_resample_tile_kernel<8, TT, false, true, Gw3Px<8>::value, GW3_TDL>)),
+                dim3((unsigned)grid), dim3(GA_THREADS), 0, st, a.x_all, a.y_all, a.idx, a.origin, a.code, a.mat,
+                a.affine, a.field, Ds, Hs, Ws, D, H, th, tw, Cin, K, s, xb, tb);
+    return launch_status();
+  }
   const bool el = op == GatherOp::elastic;
+  constexpr int GW_TILE_H = GwGeo<0>::PH * GW_PX, GW_WGW = GwGeo<0>::WGW;
   const int th = (H + GW_TILE_H - 1) / GW_TILE_H, tw = (W + GW_WGW - 1) / GW_WGW;
   if ((long long)B * D * th * tw >= (1LL << 31)) return hipErrorInvalidValue;
   if (tiled) {

@@ -376,9 +376,11 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
   //   crop     origin, code, affine                                B, Ds, Hs, Ws, D, H, W, Cin, Cpad, K
   //   warp     origin, code, mat, affine                           the same
   //   elastic  origin, code, mat, affine, field                    the same, s (log2 of the cell side)
-  // origin int32 [B][3], code int32 [B], mat int32 [B][4] (Q16), affine fp32 [B][Cin][2], field int32
-  // [B][N][N][2], N = ((H - 1) >> s) + 3.  Each may be 0 (origin, code = 0; mat = the identity; no
-  // affine) except the one named last: code for aug, origin for crop, mat for warp, field for elastic
+  //   warp3    origin, code, mat, affine, field                    the same, s (read only with a field)
+  // origin int32 [B][3], code int32 [B], mat int32 [B][4] (Q16; warp3: [B][9] over (d, h, w)), affine
+  // fp32 [B][Cin][2], field int32 [B][N][N][2], N = ((H - 1) >> s) + 3.  Each may be 0 (origin, code =
+  // 0; mat = the identity; no affine; warp3's field = no displacement) except the op's required one:
+  // code for aug, origin for crop, mat for warp and warp3, field for elastic
   struct GatherRow {
     const char* name;
     GatherOp op;
@@ -389,12 +391,13 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
   static const GatherRow kGather[] = {{"gather_batch_aug", GatherOp::aug, -1, 3, -1, 4, -1, 5, 1, "code"},
                                       {"gather_batch_crop", GatherOp::crop, 3, 4, -1, 5, -1, 6, 4, "origin"},
                                       {"gather_batch_warp", GatherOp::warp, 3, 4, 5, 6, -1, 7, 4, "mat"},
-                                      {"gather_batch_elastic", GatherOp::elastic, 3, 4, 5, 6, 7, 8, 4, "field"}};
+                                      {"gather_batch_elastic", GatherOp::elastic, 3, 4, 5, 6, 7, 8, 4, "field"},
+                                      {"gather_batch_warp3", GatherOp::warp3, 3, 4, 5, 6, 7, 8, 4, "mat"}};
   const bool f32 = kind.rfind("f32_", 0) == 0;
   for (const GatherRow& g : kGather) {
     if (kind.compare(f32 ? 4 : 0, std::string::npos, g.name) != 0) continue;
     const GatherOp op = g.op;
-    need(g.xb + 2, g.patch + 6 + (op == GatherOp::elastic), 0);
+    need(g.xb + 2, g.patch + 6 + (g.field >= 0), 0);
     auto at = [&](int i) { return i < 0 ? nullptr : vp(i); };
     GatherArgs a{};
     a.x_all = (const float*)vp(0), a.y_all = (const float*)vp(1), a.idx = (const long long*)vp(2);
@@ -403,7 +406,7 @@ Launcher make_generic(const KernelApi* A, const std::string& kind, const std::ve
     const long long* J = I.data() + g.patch;
     a.B = I[0], a.D = J[0], a.H = J[1], a.W = J[2], a.Cin = J[3], a.Cpad = J[4], a.K = J[5];
     if (g.patch == 4) a.Ds = I[1], a.Hs = I[2], a.Ws = I[3];
-    if (op == GatherOp::elastic) a.s = J[6];
+    if (g.field >= 0) a.s = J[6];
     check_msg(gather_check(op, a));
     void *xb = vp(g.xb), *tb = vp(g.xb + 1);
     if (!a.x_all || !a.y_all || !a.idx || !gather_required(op, a) || !xb || !tb)

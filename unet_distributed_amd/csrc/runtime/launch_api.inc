@@ -25,7 +25,7 @@ hipError_t cast_input_launch(const float* x, int P, int Cin, int Cpad, void* y, 
 // (K target channels per pixel, 1..4)
 hipError_t gather_batch_launch(const float* x_all, const float* y_all, const long long* idx, int B, int P, int Cin,
                                int Cpad, void* xb, void* tb, int K, hipStream_t s);
-// the four batch gathers with a per-sample transform riding on the pass (gather.h,
+// the five batch gathers with a per-sample transform riding on the pass (gather.h,
 // gather_resample.h; GatherOp and GatherArgs: conv_params.h).  aug: a code (int32 [B]: bit 0 flip
 // W, 1 flip H, 2 swap H and W, 3 flip D) and an optional per-channel affine (fp32 [B][Cin][2] =
 // {scale, shift}) on the image; crop: the same on a D x H x W patch at origin (int32 [B][3] = (d,
@@ -34,9 +34,11 @@ hipError_t gather_batch_launch(const float* x_all, const float* y_all, const lon
 // [-2^18, 2^18]): bilinear image, nearest target, zero outside the stored image; elastic: the
 // warp with a per-pixel displacement of the source coordinates, a quadratic B-spline through
 // field int32 [B][N][N][2] (2^-17 pixel, entries clamped into [-2^22, 2^22]), N = ((H - 1) >> s)
-// + 3, cells of 1 << s patch pixels.  H == W, patch <= stored on every axis.  Required besides
-// x_all, y_all, idx, xb and tb: code (aug), origin (crop), mat (warp), field (elastic); every
-// other pointer may be null (origin, code = 0; mat = the identity)
+// + 3, cells of 1 << s patch pixels; warp3: the patch resampled trilinearly through a Q16 matrix
+// over (d, h, w) (mat int32 [B][9], row-major), with the elastic displacement along (h, w) when a
+// field is given.  H == W, patch <= stored on every axis.  Required besides x_all, y_all, idx, xb
+// and tb: code (aug), origin (crop), mat (warp, warp3), field (elastic); every other pointer may
+// be null (origin, code = 0; mat = the identity; warp3's field = no displacement)
 const char* gather_check(GatherOp op, const GatherArgs& a);
 hipError_t gather_launch(GatherOp op, const GatherArgs& a, void* xb, void* tb, hipStream_t s);
 // code: optional uint32 per (pooled pixel, 8 channels) = first-argmax index per channel

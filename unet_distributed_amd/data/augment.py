@@ -38,13 +38,21 @@ matrix is the identity without rotate / scale).  The whole transform is
 ``apply_torch(*elastic_torch(x, y, origin, patch, mat, field, S), code, affine)`` -- the oracle
 of ``csrc/kernels/gather_resample.h``.  The order stays crop, resample, flip / quarter turns,
 jitter.
+
+``--augment rotate3d,scale3d`` (``--dims 3``) replaces the 2 x 2 matrix by a 3 x 3 one over
+``(d, h, w)``: :func:`draw_spatial3` draws the in-plane angle and the zoom from draw_spatial's own
+words and two out-of-plane angles (``--augment_rotate3d`` degrees) from words of their own, and
+:func:`warp3_torch` resamples the patch trilinearly through it (nearest target, zero outside the
+stored volume), with the elastic displacement along ``(h, w)`` when a field is given.  The whole
+transform is ``apply_torch(*warp3_torch(x, y, origin, patch, mat3, disp), code, affine)`` -- the
+oracle of ``gather_batch_warp3`` in ``csrc/kernels/gather_resample.h``.
 """
 
 from typing import Callable, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..config import SPATIAL_NAMES, parse_augment, parse_crop, parse_tta
+from ..config import SPATIAL3_NAMES, SPATIAL_NAMES, parse_augment, parse_crop, parse_tta
 
 FW, FH, T, FD = 1, 2, 4, 8
 # np.rot90(m, k) of the (H, W) plane for k = 0..3 as codes
@@ -227,6 +235,105 @@ def mat_of_code(code: int) -> np.ndarray:
     return np.array([0, sh, sw, 0] if code & T else [sh, 0, 0, sw], dtype=np.int32)
 
 
+# first hash lane of draw_spatial3's two out-of-plane words: past the elastic field's lanes (at most
+# 2 (2^13 + 3)^2 < 2^28 of them from 2^18 on), so codes, affines, origins, the in-plane angle, the
+# zoom and the field are the same with and without rotate3d / scale3d
+_SPATIAL3_LANE = 1 << 30
+
+
+def draw_spatial3(seed: int, step: int, sample_idx, names, rotate_deg: float = 30.0, rotate3d_deg: float = 15.0,
+                  scale_a: float = 0.25) -> np.ndarray:
+    """mat int32 [n][9]: the row-major 3 x 3 matrix in Q16 over the axes (d, h, w) that maps an
+    output offset from the patch centre to a source offset from it.  theta0, the in-plane angle
+    about the depth axis, and the zoom z come from draw_spatial's two words and are formed as it
+    forms them: theta0 with `rotate` or `rotate3d`, else 0; z with `scale` or `scale3d`, else 1.
+    theta1 (in the (d, w) plane, about the h axis) and theta2 (in the (d, h) plane, about the w
+    axis) are (2 u - 1) rotate3d_deg pi / 180 of two words of their own with `rotate3d`, else 0.
+    With Rd(t) = [[1,0,0],[0,c,-s],[0,s,c]], Rh(t) = [[c,0,-s],[0,1,0],[s,0,c]] and
+    Rw(t) = [[c,-s,0],[s,c,0],[0,0,1]]: R = Rd(theta0) Rh(theta1) Rw(theta2) in float64 and
+    mat[i][j] = rint(65536 R[i][j] / z_j), z_h = z_w = z, z_d = z with `scale3d` and 1 with `scale`.
+    With theta1 = theta2 = 0 and z_d = 1 the lower-right 2 x 2 block is draw_spatial's integers,
+    row 0 is (65536, 0, 0) and column 0 below it is 0."""
+    names = parse_augment(names) if isinstance(names, str) else tuple(names)
+    idx = np.asarray(sample_idx, dtype=np.int64).reshape(-1)
+    n = len(idx)
+    u = _unit(_hash(seed, step, idx, 2, first=_SPATIAL_LANE))
+    rot = "rotate" in names or "rotate3d" in names
+    theta0 = (2.0 * u[:, 0] - 1.0) * (float(rotate_deg) * np.pi / 180.0) if rot else np.zeros(n)
+    z = (1.0 + float(scale_a)) ** (2.0 * u[:, 1] - 1.0) if "scale" in names or "scale3d" in names else np.ones(n)
+    if "rotate3d" in names:
+        u3 = _unit(_hash(seed, step, idx, 2, first=_SPATIAL3_LANE))
+        theta1 = (2.0 * u3[:, 0] - 1.0) * (float(rotate3d_deg) * np.pi / 180.0)
+        theta2 = (2.0 * u3[:, 1] - 1.0) * (float(rotate3d_deg) * np.pi / 180.0)
+    else:
+        theta1 = theta2 = np.zeros(n)
+    return mat3_of(theta0, theta1, theta2, z, z if "scale3d" in names else np.ones(n))
+
+
+def mat3_of(theta0, theta1, theta2, z, zd) -> np.ndarray:
+    """int32 [n][9]: draw_spatial3's matrix of the angles (radians) and the zooms z (h and w) and zd
+    (d), arrays [n] or scalars."""
+    t0, t1, t2, z, zd = np.broadcast_arrays(*(np.atleast_1d(np.asarray(v, dtype=np.float64))
+                                              for v in (theta0, theta1, theta2, z, zd)))
+    n = len(t0)
+    one, zero = np.ones(n), np.zeros(n)
+
+    def m(rows):
+        return np.stack([np.stack(r, axis=1) for r in rows], axis=1)
+
+    c, s = np.cos(t0), np.sin(t0)
+    rd = m([[one, zero, zero], [zero, c, -s], [zero, s, c]])
+    c, s = np.cos(t1), np.sin(t1)
+    rh = m([[c, zero, -s], [zero, one, zero], [s, zero, c]])
+    c, s = np.cos(t2), np.sin(t2)
+    rw = m([[c, -s, zero], [s, c, zero], [zero, zero, one]])
+    r = np.einsum("nij,njk,nkl->nil", rd, rh, rw)
+    zj = np.stack([zd, z, z], axis=1)[:, None, :]
+    return (np.rint(MAT_ONE * r / zj) + 0.0).astype(np.int32).reshape(n, 9)
+
+
+def embed_mat3(mat) -> np.ndarray:
+    """int [n][9]: the 3 x 3 matrix that leaves depth alone and acts on (h, w) as `mat` int [n][4]."""
+    m = np.asarray(mat).reshape(-1, 4)
+    out = np.zeros((len(m), 9), dtype=m.dtype)
+    out[:, 0] = MAT_ONE
+    out[:, [4, 5, 7, 8]] = m
+    return out
+
+
+def warp3_torch(x, y, origin, patch, mat3, disp=None):
+    """warp_torch with depth rotated, zoomed and interpolated: the resampled patches of 5-D batch
+    tensors x [n, Ds, Hs, Ws, C] and y [n, Ds, Hs, Ws, K] (any device), `patch` = (D, H, W) voxels
+    at `origin` [n][3] (None: 0; clamped into the sample), read through `mat3` int [n][9]
+    (draw_spatial3; entries clamped into [-2^18, 2^18]).  `disp`: None, or (field, S) -- an elastic
+    field int [n][Nh][Nw][2] (draw_elastic) with cells of S patch pixels, whose displacement
+    (elastic_disp, a lattice over (h', w'), the same in every patch slice) is added to Qh and Qw.
+
+    With t = 2 d - (D-1), u = 2 h - (H-1), v = 2 w - (W-1) at patch voxel (d, h, w):
+    Qd = (od << 17) + (D-1) 65536 + m00 t + m01 u + m02 v, Qh and Qw alike from rows 1 and 2, 64-bit,
+    in 2^-17 voxel.  Image: id = Qd >> 17, fd = Qd & 0x1FFFF; s0 and s1 are warp_torch's bilinear
+    value in the slices id and id + 1 (a tap whose slice, row or column is outside the stored
+    volume is 0) and the result is s0 wd0 + s1 wd1, wd1 = fd 2^-17, wd0 = (131072 - fd) 2^-17: two
+    products and one sum, each rounded to fp32 once.  Target: y at the nearest voxel
+    ((Qd + 65536) >> 17, (Qh + 65536) >> 17, (Qw + 65536) >> 17), 0 outside.  The whole training
+    transform is ``apply_torch(*warp3_torch(...), code, affine)`` and the oracle of
+    ``gather_batch_warp3`` (``csrc/kernels/gather_resample.h``)."""
+    import torch
+    if x.dim() != 5:
+        raise ValueError("warp3_torch: 5-D samples [n, Ds, Hs, Ws, C], got %d-D" % x.dim())
+    m = np.asarray(mat3.cpu() if isinstance(mat3, torch.Tensor) else mat3)
+    if m.ndim != 2 or m.shape[1] != 9:
+        raise ValueError("warp3_torch: matrices int [n][9], got %r" % (tuple(m.shape),))
+    fn = None
+    if disp is not None:
+        field, S = disp
+        fl = field.cpu() if isinstance(field, torch.Tensor) else field
+        if len(fl) != x.shape[0]:
+            raise ValueError("warp3_torch: %d fields for %d images" % (len(fl), x.shape[0]))
+        fn = lambda n, H, W, dev: tuple(d.view(n, H, W) for d in elastic_disp(fl, (H, W), S, dev))
+    return _resample("warp3_torch", x, y, origin, patch, m, fn)
+
+
 def warp_torch(x, y, origin, patch, mat):
     """The resampled patches of batch tensors x [n, (Ds,) Hs, Ws, C] and y [n, (Ds,) Hs, Ws, K]
     (any device): `patch` = (D, H, W) (or (H, W)) voxels at `origin` [n][3] = (d, h, w) (None: 0;
@@ -248,8 +355,10 @@ def warp_torch(x, y, origin, patch, mat):
 
 
 def _resample(who, x, y, origin, patch, mat, disp):
-    """warp_torch's body; `mat` None is the identity, `disp` = None or a function (n, H, W, device)
-    -> (dh, dw) int64 [n, H, W] added to the source coordinates Qh, Qw (elastic_torch)."""
+    """warp_torch's and warp3_torch's body; `mat` None is the identity, int [n][4] the in-plane
+    matrix (depth is then a plain slice) and int [n][9] the matrix over (d, h, w); `disp` = None or a
+    function (n, H, W, device) -> (dh, dw) int64 [n, H, W] added to the source coordinates Qh, Qw
+    (elastic_torch)."""
     import torch
     n = x.shape[0]
     D, H, W = _dims3(patch)
@@ -261,7 +370,9 @@ def _resample(who, x, y, origin, patch, mat, disp):
         raise ValueError("%s: patch %r exceeds the stored sample %r" % (who, (D, H, W), (Ds, Hs, Ws)))
     if mat is None:
         mat = np.tile(np.array([MAT_ONE, 0, 0, MAT_ONE], dtype=np.int64), (n, 1))
-    m = np.asarray(mat.cpu() if isinstance(mat, torch.Tensor) else mat).reshape(-1, 4).astype(np.int64)
+    m = np.asarray(mat.cpu() if isinstance(mat, torch.Tensor) else mat)
+    full = m.ndim == 2 and m.shape[1] == 9           # the 3 x 3 matrix: depth is resampled too
+    m = m.reshape(-1, 9 if full else 4).astype(np.int64)
     if origin is None:
         org = np.zeros((n, 3), dtype=np.int64)
     else:
@@ -272,39 +383,52 @@ def _resample(who, x, y, origin, patch, mat, disp):
     dev = x.device
     m = torch.from_numpy(np.clip(m, -MAT_MAX, MAT_MAX)).to(dev)
     org = torch.from_numpy(np.clip(org, 0, np.array([Ds - D, Hs - H, Ws - W], dtype=np.int64)[None, :])).to(dev)
-    u = (2 * torch.arange(H, dtype=torch.int64, device=dev) - (H - 1)).view(1, H, 1)
-    v = (2 * torch.arange(W, dtype=torch.int64, device=dev) - (W - 1)).view(1, 1, W)
-    a = [m[:, e].view(n, 1, 1) for e in range(4)]
-    qh = (org[:, 1].view(n, 1, 1) << 17) + (H - 1) * 65536 + a[0] * u + a[1] * v
-    qw = (org[:, 2].view(n, 1, 1) << 17) + (W - 1) * 65536 + a[2] * u + a[3] * v
+    u = (2 * torch.arange(H, dtype=torch.int64, device=dev) - (H - 1)).view(1, 1, H, 1)
+    v = (2 * torch.arange(W, dtype=torch.int64, device=dev) - (W - 1)).view(1, 1, 1, W)
+    dd = torch.arange(D, dtype=torch.int64, device=dev).view(1, D, 1, 1)
+    a = [m[:, e].view(n, 1, 1, 1) for e in range(m.shape[1])]
+    oc = [org[:, e].view(n, 1, 1, 1) << 17 for e in range(3)]
+    if full:
+        t = 2 * dd - (D - 1)
+        qd = oc[0] + (D - 1) * 65536 + a[0] * t + a[1] * u + a[2] * v
+        qh = oc[1] + (H - 1) * 65536 + a[3] * t + a[4] * u + a[5] * v
+        qw = oc[2] + (W - 1) * 65536 + a[6] * t + a[7] * u + a[8] * v
+    else:
+        qh = oc[1] + (H - 1) * 65536 + a[0] * u + a[1] * v
+        qw = oc[2] + (W - 1) * 65536 + a[2] * u + a[3] * v
     if disp is not None:
         dh, dw = disp(n, H, W, dev)
-        qh, qw = qh + dh, qw + dw
-    # the D slices of every sample, pixels flattened: [n, D, Hs Ws, C]
-    dsel = org[:, 0].view(n, 1) + torch.arange(D, dtype=torch.int64, device=dev).view(1, D)
+        qh, qw = qh + dh.view(n, 1, H, W), qw + dw.view(n, 1, H, W)
+    shape = (n, D, H, W)
 
-    def slices(src):
-        s5 = src if three_d else src.unsqueeze(1)
-        s5 = s5.reshape(n, Ds, Hs * Ws, src.shape[-1])
-        return s5.gather(1, dsel.view(n, D, 1, 1).expand(n, D, Hs * Ws, src.shape[-1]))
+    def taps(src, sl, r, c):
+        """src [n, (Ds,) Hs, Ws, C] at slices sl, rows r and columns c (each broadcasts to
+        [n, D, H, W]): [n, D, H, W, C], 0 outside the stored volume."""
+        C = src.shape[-1]
+        ok = ((sl >= 0) & (sl < Ds) & (r >= 0) & (r < Hs) & (c >= 0) & (c < Ws)).expand(shape)
+        lin = ((sl.clamp(0, Ds - 1) * Hs + r.clamp(0, Hs - 1)) * Ws + c.clamp(0, Ws - 1)).expand(shape)
+        g = src.reshape(n, Ds * Hs * Ws, C).gather(1, lin.reshape(n, D * H * W, 1).expand(n, D * H * W, C))
+        return torch.where(ok.unsqueeze(-1), g.view(shape + (C,)), torch.zeros((), dtype=src.dtype, device=dev))
 
-    def taps(src, r, c):
-        """src [n, D, Hs Ws, C] at rows r and columns c [n, H, W]: [n, D, H, W, C], 0 outside."""
-        ok = (r >= 0) & (r < Hs) & (c >= 0) & (c < Ws)
-        lin = (r.clamp(0, Hs - 1) * Ws + c.clamp(0, Ws - 1)).view(n, 1, H * W, 1)
-        g = src.gather(2, lin.expand(n, D, H * W, src.shape[-1])).view(n, D, H, W, src.shape[-1])
-        return torch.where(ok.view(n, 1, H, W, 1), g, torch.zeros((), dtype=src.dtype, device=dev))
-
-    xs, ys = slices(x), slices(y)
     ih, iw = qh >> 17, qw >> 17
     fh, fw = qh & 0x1FFFF, qw & 0x1FFFF
-    sh = (n, 1, H, W, 1)
-    wh1, wh0 = (fh.float() * 2.0 ** -17).view(sh), ((131072 - fh).float() * 2.0 ** -17).view(sh)
-    ww1, ww0 = (fw.float() * 2.0 ** -17).view(sh), ((131072 - fw).float() * 2.0 ** -17).view(sh)
-    r0 = taps(xs, ih, iw) * ww0 + taps(xs, ih, iw + 1) * ww1
-    r1 = taps(xs, ih + 1, iw) * ww0 + taps(xs, ih + 1, iw + 1) * ww1
-    xo = r0 * wh0 + r1 * wh1
-    yo = taps(ys, (qh + 65536) >> 17, (qw + 65536) >> 17)
+    wh1, wh0 = (fh.float() * 2.0 ** -17).unsqueeze(-1), ((131072 - fh).float() * 2.0 ** -17).unsqueeze(-1)
+    ww1, ww0 = (fw.float() * 2.0 ** -17).unsqueeze(-1), ((131072 - fw).float() * 2.0 ** -17).unsqueeze(-1)
+
+    def bilinear(sl):
+        r0 = taps(x, sl, ih, iw) * ww0 + taps(x, sl, ih, iw + 1) * ww1
+        r1 = taps(x, sl, ih + 1, iw) * ww0 + taps(x, sl, ih + 1, iw + 1) * ww1
+        return r0 * wh0 + r1 * wh1
+
+    if full:
+        idp, fd = qd >> 17, qd & 0x1FFFF
+        wd1, wd0 = (fd.float() * 2.0 ** -17).unsqueeze(-1), ((131072 - fd).float() * 2.0 ** -17).unsqueeze(-1)
+        xo = bilinear(idp) * wd0 + bilinear(idp + 1) * wd1
+        yo = taps(y, (qd + 65536) >> 17, (qh + 65536) >> 17, (qw + 65536) >> 17)
+    else:
+        sl = org[:, 0].view(n, 1, 1, 1) + dd             # the D slices of every sample: always inside
+        xo = bilinear(sl)
+        yo = taps(y, sl, (qh + 65536) >> 17, (qw + 65536) >> 17)
     if not three_d:
         xo, yo = xo.squeeze(1), yo.squeeze(1)
     return xo.contiguous(), yo.contiguous()
@@ -489,7 +613,8 @@ def make_aug(cfg, step: int) -> Optional[Callable[[Sequence[int]], Tuple[np.ndar
     """The per-step callable a DeviceFeeder takes (dataset sample indices -> parameters),
     or None when --augment is off.  With `rotate` or `scale` named the parameters gain the warp
     matrices as a last item: (code, affine, mat).  With `elastic` named they are (code, affine,
-    mat or None, field): the matrices' slot is always there, the field (draw_elastic) comes last."""
+    mat or None, field): the matrices' slot is always there, the field (draw_elastic) comes last.
+    With `rotate3d` or `scale3d` named the matrices are draw_spatial3's [n][9] ones."""
     names = parse_augment(cfg.augment)
     if not names:
         return None
@@ -499,7 +624,7 @@ def make_aug(cfg, step: int) -> Optional[Callable[[Sequence[int]], Tuple[np.ndar
         out = draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity)
         spatial = has_spatial(names)
         if spatial:
-            out = out + (draw_spatial(cfg.seed, step, idx, names, cfg.augment_rotate, cfg.augment_scale),)
+            out = out + (_draw_mat(cfg, step, idx, names),)
         if "elastic" in names:
             out = out + (() if spatial else (None,)) + (
                 draw_elastic(cfg.seed, step, idx, side, cfg.augment_elastic, cfg.augment_elastic_cell),)
@@ -509,15 +634,29 @@ def make_aug(cfg, step: int) -> Optional[Callable[[Sequence[int]], Tuple[np.ndar
 
 
 def has_spatial(names) -> bool:
-    """Whether the --augment names hold a transform that resamples the image (rotate, scale)."""
-    return any(t in SPATIAL_NAMES for t in names)
+    """Whether the --augment names hold a transform that resamples the image through a matrix
+    (rotate, scale, rotate3d, scale3d)."""
+    return any(t in SPATIAL_NAMES or t in SPATIAL3_NAMES for t in names)
+
+
+def has_spatial3(names) -> bool:
+    """Whether the --augment names hold a transform whose matrix is the 3 x 3 one (rotate3d, scale3d)."""
+    return any(t in SPATIAL3_NAMES for t in names)
+
+
+def _draw_mat(cfg, step: int, idx, names) -> np.ndarray:
+    """The matrix slot of make_aug / make_crop_aug: [n][9] with a 3D name, else draw_spatial's [n][4]."""
+    if has_spatial3(names):
+        return draw_spatial3(cfg.seed, step, idx, names, cfg.augment_rotate, cfg.augment_rotate3d, cfg.augment_scale)
+    return draw_spatial(cfg.seed, step, idx, names, cfg.augment_rotate, cfg.augment_scale)
 
 
 def make_crop_aug(cfg, step: int, stored, table=None):
     """make_aug's sibling for --crop: dataset sample indices -> (code, affine, origin).  The
     codes are all zero and the affine None when --augment is off; the origins are draw_crop's.
     With `rotate` or `scale` named: (code, affine, origin, mat).  With `elastic` named:
-    (code, affine, origin, mat or None, field)."""
+    (code, affine, origin, mat or None, field).  With `rotate3d` or `scale3d` named the matrices
+    are draw_spatial3's [n][9] ones."""
     mode, p_fg = parse_crop(cfg.crop)
     names = parse_augment(cfg.augment)
     patch = (cfg.img_size,) * 3 if cfg.dims == 3 else (1, cfg.img_size, cfg.img_size)
@@ -525,8 +664,7 @@ def make_crop_aug(cfg, step: int, stored, table=None):
     def fn(idx):
         code, affine = draw(cfg.seed, step, idx, names, cfg.in_channels, cfg.dims, cfg.augment_intensity)
         origin, _ = draw_crop(cfg.seed, step, idx, stored, patch, mode, p_fg, table)
-        mat = draw_spatial(cfg.seed, step, idx, names, cfg.augment_rotate, cfg.augment_scale) \
-            if has_spatial(names) else None
+        mat = _draw_mat(cfg, step, idx, names) if has_spatial(names) else None
         if "elastic" in names:
             return code, affine, origin, mat, draw_elastic(cfg.seed, step, idx, patch[1:], cfg.augment_elastic,
                                                            cfg.augment_elastic_cell)

@@ -11,7 +11,7 @@ for sequential reads.  ``--num_threads`` (README.md:63) sizes the gather pool.
 import numpy as np
 import torch
 
-from .augment import apply_torch, crop_torch, elastic_torch, warp_torch
+from .augment import apply_torch, crop_torch, elastic_torch, warp3_torch, warp_torch
 
 
 class BatchLoader:
@@ -74,7 +74,8 @@ class ResidentBatch:
     optional (origin int32 [n][3] on the device, patch dims (D, H, W)): the batch is the patch
     of each stored sample at its origin (--crop), cropped before it is augmented.  An `aug` of three
     items ends in the warp matrices (mat int32 [n][4], --augment rotate / scale): the patch, or the
-    whole sample without `crop`, is resampled through them straight from the stored sample.  An `aug`
+    whole sample without `crop`, is resampled through them straight from the stored sample (mat int32
+    [n][9], --augment rotate3d / scale3d: trilinearly, through the 3 x 3 matrices).  An `aug`
     of four items (code, affine, mat or None, field int32 [n][N][N][2], --augment elastic) adds the
     elastic displacement of each sample's field, a lattice of `elastic_cell` patch pixels per cell."""
 
@@ -105,20 +106,30 @@ class ResidentBatch:
         return int(self.idx.numel()) * int(self.y_all[0].numel())
 
 
+def is_mat3(mat) -> bool:
+    """Whether `mat` holds draw_spatial3's 3 x 3 matrices, [n][9], not the in-plane [n][4] ones."""
+    return mat is not None and len(mat.shape) == 2 and int(mat.shape[1]) == 9
+
+
 def warp_batch(x, y, crop, code, affine, mat):
     """The training transform with warp matrices on the samples x [n, (Ds,) Hs, Ws, C] and y of a
     batch: `crop` = (origin [n][3], patch dims) or None (the whole sample at origin 0), then
-    warp_torch, then apply_torch(code or the identity, affine)."""
+    warp_torch -- warp3_torch for matrices of 9 entries (--augment rotate3d / scale3d) -- then
+    apply_torch(code or the identity, affine)."""
     origin, patch = crop if crop is not None else (None, tuple(x.shape[1:-1]))
-    x, y = warp_torch(x, y, origin, patch, mat)
+    x, y = warp3_torch(x, y, origin, patch, mat) if is_mat3(mat) else warp_torch(x, y, origin, patch, mat)
     return apply_torch(x, y, code if code is not None else np.zeros(x.shape[0], dtype=np.int32), affine)
 
 
 def elastic_batch(x, y, crop, code, affine, mat, field, S: int = 32):
     """warp_batch with an elastic field (cells of S patch pixels): elastic_torch, whose `mat` may be
-    None (the identity), then apply_torch(code or the identity, affine)."""
+    None (the identity) -- warp3_torch with the field for matrices of 9 entries -- then
+    apply_torch(code or the identity, affine)."""
     origin, patch = crop if crop is not None else (None, tuple(x.shape[1:-1]))
-    x, y = elastic_torch(x, y, origin, patch, mat, field, S)
+    if is_mat3(mat):
+        x, y = warp3_torch(x, y, origin, patch, mat, (field, S))
+    else:
+        x, y = elastic_torch(x, y, origin, patch, mat, field, S)
     return apply_torch(x, y, code if code is not None else np.zeros(x.shape[0], dtype=np.int32), affine)
 
 
@@ -166,7 +177,8 @@ class DeviceFeeder:
         """Index tensor and augmentation parameters in one small non-blocking copy:
         [idx int64 | affine fp32 | code int32 | origin int32 | mat int32 | field int32] ->
         (idx, (code, affine)) device views, and with `origin` (int [n][3], --crop) the origin view
-        as a third item.  With `mat` (int [n][4], --augment rotate / scale) the second item is
+        as a third item.  With `mat` (int [n][4], --augment rotate / scale, or [n][9], rotate3d /
+        scale3d: the rows keep their width) the second item is
         (code, affine, mat); with `field` (int [n][N][N][2], --augment elastic) it is (code, affine,
         mat or None, field): the field rides at the end, every other view keeps its offset."""
         n = len(sorted_idx)
@@ -176,7 +188,8 @@ class DeviceFeeder:
         if origin is not None:
             parts.append(np.ascontiguousarray(origin, dtype=np.int32).reshape(-1).view(np.uint8))
         if mat is not None:
-            parts.append(np.ascontiguousarray(mat, dtype=np.int32).reshape(-1).view(np.uint8))
+            mat = np.ascontiguousarray(mat, dtype=np.int32).reshape(n, -1)
+            parts.append(mat.reshape(-1).view(np.uint8))
         if field is not None:
             field = np.ascontiguousarray(field, dtype=np.int32)
             parts.append(field.reshape(-1).view(np.uint8))
@@ -187,8 +200,8 @@ class DeviceFeeder:
         cd = buf[8 * n + na:8 * n + na + 4 * n].view(torch.int32)
         at = 8 * n + na + 4 * n
         no = 12 * n if origin is not None else 0
-        nm = 16 * n if mat is not None else 0
-        dev = (cd, af) if mat is None else (cd, af, buf[at + no:at + no + nm].view(torch.int32).view(n, 4))
+        nm = mat.nbytes if mat is not None else 0
+        dev = (cd, af) if mat is None else (cd, af, buf[at + no:at + no + nm].view(torch.int32).view(mat.shape))
         if field is not None:
             dev = dev[:2] + (dev[2] if mat is not None else None,
                              buf[at + no + nm:at + no + nm + field.nbytes].view(torch.int32).view(field.shape))

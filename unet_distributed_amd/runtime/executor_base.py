@@ -284,7 +284,8 @@ class ExecutorBase:
         launch (kernels/gather_resample.h).  An `aug` of four items (code or None, affine or None, mat or
         None, field int32 [B][N][N][2]) adds the elastic displacement of each sample's field to
         the warp's source coordinates (the same kernels): `elastic_cell` is the side S of a
-        lattice cell in patch pixels and N = ((H - 1) >> log2 S) + 3."""
+        lattice cell in patch pixels and N = ((H - 1) >> log2 S) + 3.  A `mat` int32 [B][9] (3D
+        executors) resamples trilinearly through 3 x 3 matrices over (d, h, w), with or without a field."""
         if aug is None and crop is None:
             return self._load_plain(x_all, y_all, idx, stream)
         self._check_indexed(x_all, y_all, idx)
@@ -293,21 +294,24 @@ class ExecutorBase:
         self.C.generic(self._op(name), ptrs, ints, [], native.stream_handle(stream), self.dt_id)
 
     def _gather_args(self, x_all, y_all, idx, aug, crop, elastic_cell: int = 32):
-        """(op name, ptrs, ints) of the gather_batch_aug / _crop / _warp / _elastic launch (bindings.cpp)
+        """(op name, ptrs, ints) of the gather_batch_aug / _crop / _warp / _elastic / _warp3 launch (bindings.cpp)
         that loads the batch from the resident dataset [N, (Ds,) Hs, Ws, Cin]: `aug` = (code or
         None, affine or None[, mat int32 [B][4] or None]) or None, `crop` = (origin int32 [B][3],
         patch dims (D, H, W)) or None.  With `mat` it is the warp, whose patch without `crop` is
         the executor's input at origin 0, which the stored sample must hold; else with `crop`
         the crop; else the augmenting gather of whole samples, which needs its codes.  An `aug` of
         four items ends in the elastic field (int32 [B][N][N][2], cells of `elastic_cell` patch
-        pixels) and selects the elastic op, whose `mat` may be None."""
+        pixels) and selects the elastic op, whose `mat` may be None.  A `mat` int32 [B][9] (the
+        3 x 3 matrices over (d, h, w)) selects gather_batch_warp3, with or without a field."""
         code, affine = aug[:2] if aug is not None else (None, None)
         mat = aug[2] if has_mat(aug) else None
         field = aug[3] if has_field(aug) else None
         if aug is not None and len(aug) > 3 and field is None:
             raise ValueError("an augmentation of four items ends in the elastic field")
-        name = "gather_batch_elastic" if field is not None else "gather_batch_warp" if mat is not None \
-            else "gather_batch_crop" if crop is not None else "gather_batch_aug"
+        mat3 = mat is not None and mat.dim() == 2 and mat.shape[1] == 9
+        name = "gather_batch_warp3" if mat3 else "gather_batch_elastic" if field is not None \
+            else "gather_batch_warp" if mat is not None else "gather_batch_crop" if crop is not None \
+            else "gather_batch_aug"
         B, cin, dev = self.B, self.spec.in_channels, x_all.device
         stored = (x_all.shape[1] if x_all.dim() == 5 else 1, x_all.shape[-3], x_all.shape[-2])
         origin, patch = crop if crop is not None else (None, self.sdims(1))
@@ -328,8 +332,12 @@ class ExecutorBase:
                 raise ValueError("elastic field: a contiguous int32 [%d][%d][%d][2] tensor on %s (cell %d)"
                                  % (B, N, N, dev, elastic_cell))
         if mat is not None:
-            if mat.dtype != torch.int32 or tuple(mat.shape) != (B, 4) or mat.device != dev or not mat.is_contiguous():
-                raise ValueError("warp matrices: a contiguous int32 [%d][4] tensor on %s" % (B, dev))
+            # (a 2D executor takes the in-plane matrices alone, and its message says so)
+            shapes = ((B, 4), (B, 9)) if self.dims == 3 else ((B, 4),)
+            if mat.dtype != torch.int32 or tuple(mat.shape) not in shapes or mat.device != dev \
+                    or not mat.is_contiguous():
+                raise ValueError("warp matrices: a contiguous int32 [%d][4] %son %s" % (
+                    B, "tensor " if self.dims != 3 else "(in-plane) or [%d][9] (over d, h, w) tensor " % B, dev))
         if (origin is not None or name == "gather_batch_crop") and (
                 origin.dtype != torch.int32 or tuple(origin.shape) != (B, 3) or origin.device != dev
                 or not origin.is_contiguous()):
@@ -344,7 +352,7 @@ class ExecutorBase:
         own = {"origin": origin, "code": code, "mat": mat, "affine": affine, "field": field}
         ptrs = [x_all, y_all, idx] + [own[k] for k in row.slots] + [self.bufs["x"], self.target]
         ints = [B] + (list(stored) if row.patch == 4 else []) + list(patch) + [cin, self.cpad, self.K] + (
-            [slog] if "field" in row.slots else [])
+            [slog if field is not None else 0] if "field" in row.slots else [])
         return name, [0 if t is None else _ptr(t) for t in ptrs], ints
 
     # ------------------------------------------------------------------ evaluation

@@ -36,7 +36,7 @@ WGRAD_WRITES = ("slab", "bias_slab")
 
 class GatherRow(NamedTuple):
     """Layout of one batch gather's generic op (bindings.cpp): ptrs = x_all, y_all, idx, `slots`,
-    xb, tb; ints = B, (Ds, Hs, Ws when `patch` is 4,) D, H, W, Cin, Cpad, K (, s for the elastic op)."""
+    xb, tb; ints = B, (Ds, Hs, Ws when `patch` is 4,) D, H, W, Cin, Cpad, K (, s for the ops with a field)."""
     slots: Tuple[str, ...]      # the op's own pointers, in order
     nints: int
     patch: int                  # index of the patch's D in ints
@@ -51,6 +51,7 @@ GATHER_OPS = {
     "gather_batch_crop": GatherRow(("origin", "code", "affine"), 10, 4),
     "gather_batch_warp": GatherRow(("origin", "code", "mat", "affine"), 10, 4),
     "gather_batch_elastic": GatherRow(("origin", "code", "mat", "affine", "field"), 11, 4),
+    "gather_batch_warp3": GatherRow(("origin", "code", "mat", "affine", "field"), 11, 4),
 }
 
 

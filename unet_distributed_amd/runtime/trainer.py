@@ -241,10 +241,14 @@ class Trainer:
         self.eval_sliding = tested != model
         names = parse_augment(cfg.augment)
         self.aug_ranges = {}
-        if "rotate" in names:
+        if "rotate" in names or "rotate3d" in names:
             self.aug_ranges["rotate_deg"] = [-float(cfg.augment_rotate), float(cfg.augment_rotate)]
-        if "scale" in names:
+        if "rotate3d" in names:         # the two out-of-plane angles
+            self.aug_ranges["rotate3d_deg"] = [-float(cfg.augment_rotate3d), float(cfg.augment_rotate3d)]
+        if "scale" in names or "scale3d" in names:
             self.aug_ranges["scale"] = [1.0 / (1.0 + cfg.augment_scale), 1.0 + cfg.augment_scale]
+        if "scale3d" in names:          # the zoom acts along depth too
+            self.aug_ranges["scale_depth"] = True
         if "elastic" in names:
             self.aug_ranges["elastic"] = {"sigma_px": float(cfg.augment_elastic), "cell": int(cfg.augment_elastic_cell)}
         self.sampler = datasets.EpochSampler(len(self.x_train), cfg.batch_size, self.rank, self.world, cfg.seed)
@@ -257,11 +261,13 @@ class Trainer:
                                          else "streamed from host (pinned, double-buffered)"))
             if cfg.augment:
                 names = parse_augment(cfg.augment)
-                print("Training augmentation: %s%s%s%s%s" % (
+                print("Training augmentation: %s%s%s%s%s%s" % (
                     ", ".join(names), " (amplitude %g)" % cfg.augment_intensity if "intensity" in names else "",
-                    " (rotate +-%g deg)" % cfg.augment_rotate if "rotate" in names else "",
-                    " (scale %.4g..%.4g)" % (1.0 / (1.0 + cfg.augment_scale), 1.0 + cfg.augment_scale)
-                    if "scale" in names else "",
+                    " (rotate +-%g deg)" % cfg.augment_rotate if "rotate" in names or "rotate3d" in names else "",
+                    " (out of plane +-%g deg)" % cfg.augment_rotate3d if "rotate3d" in names else "",
+                    " (scale %.4g..%.4g%s)" % (1.0 / (1.0 + cfg.augment_scale), 1.0 + cfg.augment_scale,
+                                              ", depth too" if "scale3d" in names else "")
+                    if "scale" in names or "scale3d" in names else "",
                     " (elastic sigma %g px, cell %d)" % (cfg.augment_elastic, cfg.augment_elastic_cell)
                     if "elastic" in names else ""))
             if self.crop_mode:
