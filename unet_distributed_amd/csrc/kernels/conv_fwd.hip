@@ -1166,7 +1166,9 @@ const char* conv_fwd_prepare(ConvFwdParams& p) {
     const long long opx = (long long)p.OD * p.OH * p.OW;
     const long long lim = (1LL << 31) - 64;
     long long span = img * p.N;                       // bytes a launch addresses from one base
-    if (win_tile(t) || t == 13 || t == 14) span = img;
+    // (a 512-pixel window on 16-wide rows is two images, addressed from the first)
+    if (win_tile(t) && p.OW == 16 && win_b512_eligible(p)) span = 2 * img;
+    else if (win_tile(t) || t == 13 || t == 14) span = img;
     else if (t >= 1 && t <= 5) span = img * (256 / opx + 2 < p.N ? 256 / opx + 2 : p.N);
     if (span >= lim) return "conv_fwd: input exceeds the 2 GiB reach of one buffer base (split the batch)";
   }
@@ -1195,7 +1197,7 @@ int conv_fwd_pick(const ConvFwdParams& p) {
   // row-window 512x32 wins at every level it applies to (16..128 wide), measured
   // 1.1-2.1x over the implicit-GEMM tiles (profiles/r1_conv_tiles.md); the 512x64
   // variant took 287 registers unbounded (1 wave/SIMD) and never won -- bounded to 256 it
-  // runs two workgroups per CU on 32 / 64-wide rows (conv_win.h win_b512_eligible)
+  // runs two workgroups per CU on 16 / 32 / 64-wide rows (conv_win.h win_b512_eligible)
   if (p.tile != 8 && win_eligible(p)) return 6;
   if (p.tile != 8 && win_first_eligible(p)) return 9;
   if (p.tile != 8 && img8_eligible(p)) return 13;
@@ -1220,6 +1222,8 @@ void conv_stat_tiles(const ConvFwdParams& p, int* rows, int* tile_px) {
   switch (t) {
     case 6:
     case 12: {       // row window: R rows x (segment) width, tiles in (row group, segment) order
+      // (the statistics epilogues, modes 3 / 4, are not win_b512_eligible: their windows are
+      // 256 pixels -- on 16-wide rows one image -- whatever win_bm2 says)
       const int W = p.OW > 128 ? 128 : p.OW;
       const int R = win_pfu_eligible(p) ? 2 : win_rows(p);   // (the persistent tconv-on-load window: 2 rows)
       if (p.nz && p.C2) return;

@@ -177,7 +177,8 @@ struct ConvFwdParams {
                               // (conv_win_cp_kernel); >= 2: also 128-wide rows, 3D or two or more
                               // chunks (conv_win_cp128_kernel)
   int win_bm2;                // 64-channel row windows of 512 pixels instead of 256 (conv_win.h
-                              // win_b512_eligible): bit 0 on 32-wide rows, bit 1 on 64-wide rows
+                              // win_b512_eligible): bit 0 on 32-wide rows, bit 1 on 64-wide rows,
+                              // bit 2 on 16-wide rows (two whole 16 x 16 images per window)
   HeadGrad hg;               // 2D row-window data gradient of the head input: src1 (dY) formed
                               // on load (one 32-channel chunk), see HeadGrad
   // Space-to-depth source (2D row-window, composite transposed-conv data gradient):

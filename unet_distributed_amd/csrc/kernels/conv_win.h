@@ -33,14 +33,20 @@ inline int win_bn(const ConvFwdParams& p) {
 // forward (pool epilogue too), data-gradient (masks, pool route) or generic epilogue.  The
 // statistics and dgrad-norm epilogues (one statistics row per 256-pixel window), the
 // operand transforms 1 / 2 / 3 / 5, the fused weight gradient and 3D keep 256 pixels.
+// Bit 2: 16-wide rows of 16 x 16 images, where a 512-pixel window is two whole images (the
+// kernel cuts the two taps that would cross the seam between them); an even number of
+// images, no space-to-depth source -- an odd image count keeps 256 pixels.
 inline bool win_b512_eligible(const ConvFwdParams& p) {
-  const int bit = p.OW == 32 ? 1 : (p.OW == 64 ? 2 : 0);
+  const int bit = p.OW == 32 ? 1 : (p.OW == 64 ? 2 : (p.OW == 16 ? 4 : 0));
   const int ep = conv_epi_mode(p);
-  return (p.win_bm2 & bit) && win_bn(p) == 64 && p.KD == 1 && p.OD == 1 && p.OH % (512 / p.OW) == 0 &&
+  if (!(p.win_bm2 & bit)) return false;
+  const bool rows_ok = p.OW == 16 ? (p.OH == 16 && (p.N * p.OH) % 32 == 0 && !p.s2d) : p.OH % (512 / p.OW) == 0;
+  return win_bn(p) == 64 && p.KD == 1 && p.OD == 1 && rows_ok &&
          (ep == EPI_FWD || ep == EPI_DGRAD || ep == EPI_GENERIC) && !p.xform && !p.hg.prob && !p.ut.x &&
          !p.fw.x && !p.head_w;
 }
-// Window pixels: 256 for 16-wide rows (one whole image: a window never spans two) and for
+// Window pixels: 256 for 16-wide rows (one whole 16 x 16 image; with win_bm2 bit 2 the
+// 64-channel tile takes two whole images, 512 pixels) and for
 // the 64-channel tile (4 x 4 accumulator fragments per wave), else 512.  The 64-channel
 // tile at 512 pixels (win_b512_eligible: 8 x 4 accumulators = 128 registers + 48 of weight
 // fragments under a 256-register bound, 77 / 79 KB LDS at W = 32 / 64 -- still two
@@ -49,6 +55,9 @@ inline bool win_b512_eligible(const ConvFwdParams& p) {
 // window), -0.6 ms per step (profiles/r18_win512.md).  Of a workgroup's ~13 us outside its
 // chunks only ~12 % amortises (the rest is per-pixel staging and stores); the other part
 // of the gain is the 36 KB weight image staged per chunk half as often per pixel.
+// On 16-wide rows (bit 2, two 16 x 16 images per window: 79 pieces of LDS-DMA per chunk for
+// 1152 MFMAs instead of 59 for 576) the nine level-4 launches fell 5.9 % summed, the step
+// 0.5 ms (profiles/r23_win512_w16.md).
 // (A 256-pixel 32-channel window on 32..128-wide rows -- three workgroups per CU --
 // measured -0.4 % at W = 64 and -1 % at 128 and was dropped; a pipelined 8-wave window
 // with double-buffered chunks, one workgroup per CU, measured -2..-21 % per launch at
@@ -116,11 +125,12 @@ inline int win_grid(const ConvFwdParams& p) {
   return ((rows + R - 1) / R) * (p.OW / W) * (p.Cout / win_bn(p));
 }
 // (BN, BM, row width) combinations win_bn / win_bm can select (the 64-channel tile also
-// on 128-wide rows: tile 12 forces it there for tests; its 512-pixel window on 32 / 64-wide
-// rows only -- 16-wide rows would span two images, 128-wide ones need 90 KB of LDS)
+// on 128-wide rows: tile 12 forces it there for tests; its 512-pixel window on 16 / 32 /
+// 64-wide rows -- on 16-wide rows it is two whole 16 x 16 images, plain and concat sources
+// only; 128-wide rows would need 90 KB of LDS)
 template <int BN, int BM>
 constexpr bool win_tile_built(int W) {
-  return BN == 64 ? (BM == 256 || (BM == 512 && (W == 32 || W == 64))) : (BM == 256 ? W == 16 : W != 16);
+  return BN == 64 ? (BM == 256 || (BM == 512 && (W == 16 || W == 32 || W == 64))) : (BM == 256 ? W == 16 : W != 16);
 }
 
 template <int BN, int BM>
@@ -249,6 +259,7 @@ __global__ void __launch_bounds__(NTHR, (BN == 64 && BM == 512) ? 2 : 1) conv_wi
   static_assert(NCS <= 4 && 4 % NCS == 0 && RW * TC == TM, "strip map");
   using Map = StripTiles<W, RW, TC, NCS>;
   const int r0 = (wave / NCS) * RW, c0 = (wave % NCS) * 16 * TC;
+  // (W == 16, BM == 512: R == 2 H, the window is two whole images -- SEAM below)
   // H % R == 0 (win_eligible): a window never spans two images, so the only rows of
   // another image are the halo rows above / below it, which the DMA fills with zeros
   // (the 'same' padding) -- the tap loop needs no image-edge branches at all, and the
@@ -275,6 +286,22 @@ __global__ void __launch_bounds__(NTHR, (BN == 64 && BM == 512) ? 2 : 1) conv_wi
   // held in registers and every halo-row fragment feeds up to three output rows
   // tmask: taps (bit 3 dh + dw) of this chunk that are not structurally zero (XF 4);
   // a compile-time 0x1ff everywhere else, so the tests fold away
+  // W == 16, BM == 512 (win_b512_eligible bit 2): the window is two whole 16 x 16 images A, B
+  // and the halo one linear run of 34 rows -- zeros, A's rows 0..15, B's rows 0..15, zeros
+  // (top_in / bot_in are false, the DMA base is A's first pixel).  Two fragments would cross
+  // the seam: wave 1's halo row RW + 1 (B's row 0; its only consumer is A's row 15, dh = 2)
+  // and wave 2's halo row 0 (A's row 15; its only consumer is B's row 0, dh = 0).  They are
+  // read from the zero rows 33 / 0 of the halo image instead, 16 rows away -- a wave-uniform
+  // offset on two fragment addresses: the MFMAs and their order stay those of the 256-pixel
+  // window, which multiplies the DMA's zero padding there, so outputs are bit-identical and
+  // the chunk stays one basic block.
+  constexpr bool SEAM = W == 16 && BM == 512;
+  int seam_lo = 0, seam_hi = 0;
+  if constexpr (SEAM) {
+    static_assert(!SEAM || (R == 32 && RW == 8 && HR == 34), "two 16-row images, one wave per 8 rows");
+    seam_lo = wave == 2 ? -16 * ROWB : 0;
+    seam_hi = wave == 1 ? 16 * ROWB : 0;
+  }
   auto chunk_mfmas = [&](const uint32_t tmask) {
 #pragma unroll
     for (int dw = 0; dw < 3; ++dw) {
@@ -288,7 +315,9 @@ __global__ void __launch_bounds__(NTHR, (BN == 64 && BM == 512) ? 2 : 1) conv_wi
       for (int hr = 0; hr < RW + 2; ++hr) {
 #pragma unroll
         for (int ci = 0; ci < TC; ++ci) {
-          const h16x8 xf = *(const h16x8*)(Xs + xbase[dw] + hr * ROWB + ci * 16 * 64);
+          const char* xp = Xs + xbase[dw] + hr * ROWB + ci * 16 * 64;
+          if constexpr (SEAM) xp += hr == 0 ? seam_lo : (hr == RW + 1 ? seam_hi : 0);
+          const h16x8 xf = *(const h16x8*)xp;
 #pragma unroll
           for (int dh = 0; dh < 3; ++dh) {
             const int ri = hr - dh;
@@ -1733,9 +1762,13 @@ hipError_t launch_win_b512(const ConvFwdParams& p, hipStream_t s) {
   const int grid = win_grid(p);
   const int epi = conv_epi_mode(p);
   if (p.s2d) {                          // space-to-depth dgrad source (conv_fwd_prepare checks the shape)
-    if (epi != EPI_DGRAD || p.C2) return hipErrorInvalidValue;
-    UNET_LAUNCH((conv_win_kernel<W, 64, 512, false, EPI_DGRAD, GEO_2D, 4>), dim3(grid), dim3(NTHR), 0, s, p);
-    return launch_status();
+    if constexpr (W == 16) {            // (two-image windows: plain and concat sources only)
+      return hipErrorInvalidValue;
+    } else {
+      if (epi != EPI_DGRAD || p.C2) return hipErrorInvalidValue;
+      UNET_LAUNCH((conv_win_kernel<W, 64, 512, false, EPI_DGRAD, GEO_2D, 4>), dim3(grid), dim3(NTHR), 0, s, p);
+      return launch_status();
+    }
   }
 #define B512_EPI(CC)                                                                                      \
   if (epi == EPI_FWD)                                                                                     \
@@ -1761,6 +1794,7 @@ static hipError_t launch_win_tile(const ConvFwdParams& p, hipStream_t s);
 template <int BN, int BM>
 hipError_t launch_win(const ConvFwdParams& p, hipStream_t s) {
   if constexpr (BN == 64 && BM == 512) {
+    if (p.OW == 16) return launch_win_b512<16>(p, s);
     return p.OW == 32 ? launch_win_b512<32>(p, s) : (p.OW == 64 ? launch_win_b512<64>(p, s) : hipErrorInvalidValue);
   } else {
     if constexpr (BN == 64 && BM == 256) {

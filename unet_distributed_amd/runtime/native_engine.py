@@ -86,8 +86,11 @@ def _r64(k: int) -> int:
 #                current chunk's MFMAs (conv_win.h conv_win_cp_kernel) (1; 0 off)
 #   win_bm2      64-channel row windows of 512 pixels instead of 256 (conv_win.h win_b512_eligible):
 #                bit 0 = 32-wide rows, bit 1 = 64-wide rows (there the LDS-DMA chunk loop replaces
-#                win_cp's window); bit-identical results (3: the 32-wide launches -10.3 %, the
-#                64-wide ones -8.8 % summed, -0.6 ms on the step, profiles/r18_win512.md; 0 off)
+#                win_cp's window), bit 2 = 16-wide rows of 16 x 16 images (a window is two whole
+#                images; an odd image count keeps 256 pixels); bit-identical results (7: the
+#                32-wide launches -10.3 %, the 64-wide ones -8.8 % summed, -0.6 ms on the step,
+#                profiles/r18_win512.md; the 16-wide ones -5.9 % summed, -0.5 ms on the step,
+#                profiles/r23_win512_w16.md; 0 off)
 #   dz_split     normalised layers on 16..64-wide rows whose dz only their own data and weight
 #                gradients read: both form it on load (conv_win.h XF 2, wgrad_win_kernel DZ) (0:
 #                measured slower, r6_bench_history.md -- the consumers' per-window z loads and
@@ -101,7 +104,7 @@ def _r64(k: int) -> int:
 ENGINE_DEFAULTS = dict(dual_stream=1, fwd_streams=2, head_fuse=1, head_onload=1, tconv_fused=2, tconv_wa=1,
                        tconv_onload=1, fwd_offset=6, wg_target=512, dw_fuse=1, dw_wgs=512, win_pf=8, win_cp=1,
                        dz_split=0, head_wsum=1, xf_drop=0, wg_pf=1, win_cp3=2, skip_onload=1,
-                       route3=1, tail3=0, dw_pipe=1, win_bm2=3)
+                       route3=1, tail3=0, dw_pipe=1, win_bm2=7)
 
 
 class Fusion:
